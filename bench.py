@@ -12,7 +12,18 @@ frame buffer are resident in HBM before the timed region; no host copies inside 
          the timing only). The line also carries the 1080p frame split the same way ("c3_frame").
   --frame WxH overrides the frame.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including:
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what the headline figure needs: scene setup,
+the prewarm and warmup frames, the K timed frames, the outputs of --dump-outputs, and the result line (`value`,
+`ms_per_step`, the configuration). Everything else below -- the cold rate, the lone-frame kernel time, the second
+frame size, the C2 / C5 side lines, the moving camera, the roofline, the parity checks, the end-to-end frame and
+the CPU baseline -- runs only with --full (where the --no-* options still drop single legs).
+  --dump-outputs DIR: after the timed frames, the frame a caller of the timed path receives from its last step
+            (rt_frame_download of the last timed frame: float32 rgb [H, W, 3]) as DIR/rgb.npy; a frame over
+            64 MB as a fixed seeded sample of its pixels (DIR/rgb.npy [n, 3] + DIR/rgb_pixel_index.npy). Scene
+            (seed 12345), camera and lights are fixed, so two builds can be compared output for output.
+
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, steps, ms_per_step (milliseconds per
+timed step), the configuration and the build's identity; with --full also:
   roofline: HBM roofline of the dominant kernel (k_primary_fused). achieved = the packet algorithm's bytes
             per launch (64-B node record per wave per visited node, 64-B triangle record per wave per
             tested triangle -- the counting run's wave fetch counts -- plus per hit lane the 64-B hit
@@ -492,8 +503,67 @@ def moving_camera(rt, make_scene, sc4, W, H, mode, case, steps, warmup, sync_dev
     return out
 
 
-def timed_frames(rt, sc, cam, W, H, mode, shard, steps, warmup, barrier, sync_device, prewarm_ms=0.0, path=None):
-    """W untimed warmup frames, then EXACTLY `steps` timed frames bracketed by barrier + device synchronisation.
+DUMP_CAP_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files of a run together stay under this
+DUMP_SEED = 12345
+
+
+def dump_arrays(out_dir, arrays, cap=DUMP_CAP_BYTES, suffix=""):
+    """--dump-outputs: each array of `arrays` ({name: per-pixel array [H, W, c] or [H, W]}) as
+    <out_dir>/<name><suffix>.npy in float32 (float64 stays float64). When the arrays together exceed `cap` bytes,
+    each is cut to the same fixed sample of its pixels -- the sorted first n of a seeded permutation (DUMP_SEED),
+    so every run and every build samples the same pixels -- and the pixels' row-major indices go to
+    <out_dir>/<name>_pixel_index<suffix>.npy (float64, exact). Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+              for k, v in arrays.items()}
+    written = {}
+    share = cap // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            px = a.reshape(a.shape[0] * a.shape[1], -1)
+            n = share // (px.shape[1] * a.itemsize + 8)  # a pixel's values + its float64 index
+            idx = np.sort(np.random.default_rng(DUMP_SEED).permutation(len(px))[:n])
+            a = np.ascontiguousarray(px[idx])
+            np.save(os.path.join(out_dir, f"{name}_pixel_index{suffix}.npy"), idx.astype(np.float64))
+            written[f"{name}_pixel_index{suffix}.npy"] = [len(idx)]
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+        written[f"{name}{suffix}.npy"] = list(a.shape)
+    return written
+
+
+def enqueue_cost_ms(rt, sc, cams, W, H, mode, shard):
+    """Host cost of queueing one frame (rt_render_async through the Python binding), frames not waited on."""
+    t1 = time.perf_counter()
+    for c in cams:
+        sc.render_async(c, rt.DEFAULT_LIGHTS, W, H, mode=mode, shard=shard)
+    ms = (time.perf_counter() - t1) / len(cams) * 1e3
+    sc.synchronize()
+    return ms
+
+
+MAX_PENDING_FRAMES = 2048  # rt_render_async refuses more renders than this between two rt_synchronize calls
+
+
+def merge_stats(a, b):
+    """(totals, [per device]) of two consecutive rt_synchronize_devices read-outs as one: kernel times and launch
+    counts add up, everything else (the rays of a frame, a counting run's counters) is the later read-out's."""
+    if a is None:
+        return b
+    def add(x, y):
+        out = dict(y)
+        for key in ("kernel_ms", "trace_kernel_ms", "launches"):
+            if key in x or key in y:
+                out[key] = x.get(key, 0) + y.get(key, 0)
+        return out
+    return add(a[0], b[0]), [add(x, y) for x, y in zip(a[1], b[1])]
+
+
+def timed_frames(rt, sc, cam, W, H, mode, shard, steps, warmup, barrier, sync_device, prewarm_ms=0.0, path=None,
+                 enqueue=True):
+    """W untimed warmup frames, then EXACTLY `steps` timed frames bracketed by barrier + device synchronisation
+    (any number of steps: see MAX_PENDING_FRAMES below).
+    enqueue: afterwards also measure the host's cost of queueing a frame (up to 3 more, untimed frames) into
+    st["enqueue_ms"]; without it the scene's last frame is the last timed one.
     prewarm_ms: before the warmup frames, frames of the same workload rendered back to back (untimed) for that
     long, so that the timed frames see the GPU in its loaded state rather than just out of idle (a steady-state
     rate; the cold start is in profiles/ab/r05_prewarm_ab.txt); their count is returned as st["prewarm_frames"].
@@ -508,22 +578,30 @@ def timed_frames(rt, sc, cam, W, H, mode, shard, steps, warmup, barrier, sync_de
             sc.render_async(nxt(), rt.DEFAULT_LIGHTS, W, H, mode=mode, shard=shard)
         n_pw += 4
         sc.synchronize()
-    for _ in range(warmup):
+    for k in range(warmup):
+        if k and k % MAX_PENDING_FRAMES == 0:
+            sc.synchronize()
         sc.render_async(nxt(), rt.DEFAULT_LIGHTS, W, H, mode=mode, shard=shard)
     sc.synchronize()
     cams = path.take(steps) if path is not None else [cam] * steps
     barrier()
     sync_device()
+    done = None
     t0 = time.perf_counter()
-    for c in cams:
+    for k, c in enumerate(cams):
+        # the library's bound on queued frames: a longer run is drained inside the window after every
+        # MAX_PENDING_FRAMES frames (one pipeline drain and that many frames' event read-out, ~1 us each, per
+        # MAX_PENDING_FRAMES frames: well under 1% of their time); up to that many steps nothing is added
+        if k and k % MAX_PENDING_FRAMES == 0:
+            done = merge_stats(done, sc.synchronize_devices())
         sc.render_async(c, rt.DEFAULT_LIGHTS, W, H, mode=mode, shard=shard)
     # every device of the scene drained (rt_render_async returns once each device's share is queued, so a
-    # device synchronise covers every frame); the frames' event times are read after the clock stops
+    # device synchronise covers every frame); the last frames' event times are read after the clock stops
     # (rt_synchronize_devices: ~1 us of host time per frame, not part of a frame; profiles/ab/r05_sync_readout_ab.txt)
     sync_device()
     barrier()
     el = time.perf_counter() - t0
-    st, per = sc.synchronize_devices()
+    st, per = merge_stats(done, sc.synchronize_devices())
     st["per_device"] = per
     # the window holds every timed frame of every device: a frame slot's stream runs its frames one
     # after the other, each frame's HIP-event interval (start event -> end event, both recorded on that stream
@@ -537,13 +615,9 @@ def timed_frames(rt, sc, cam, W, H, mode, shard, steps, warmup, barrier, sync_de
             raise RuntimeError(f"device {k}: frames' kernel time {p['kernel_ms']:.3f} ms exceeds {slots} slots x the "
                                f"timed window {el * 1e3:.3f} ms: frames not drained")
     st["prewarm_frames"] = n_pw
-    # host cost of queueing one frame (rt_render_async through the Python binding), frames not waited on
-    more = path.take(min(steps, 3)) if path is not None else [cam] * min(steps, 3)
-    t1 = time.perf_counter()
-    for c in more:
-        sc.render_async(c, rt.DEFAULT_LIGHTS, W, H, mode=mode, shard=shard)
-    st["enqueue_ms"] = (time.perf_counter() - t1) / len(more) * 1e3
-    sc.synchronize()
+    if enqueue:
+        more = path.take(min(steps, 3)) if path is not None else [cam] * min(steps, 3)
+        st["enqueue_ms"] = enqueue_cost_ms(rt, sc, more, W, H, mode, shard)
     return el, st
 
 
@@ -569,6 +643,13 @@ def main():
     ap.add_argument("--frame", default=None, help="WxH; default 1920x1080 on 1 GPU (C3), 3840x2160 split over N>1 (C4)")
     ap.add_argument("--mode", choices=["primary", "full"], default="primary")
     ap.add_argument("--scene", default="soup", help="soup | bunny")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (cold rate, lone-frame kernel "
+                         "time, second frame size, C2 / C5, moving camera, roofline, parity against the committed "
+                         "oracle digests, end-to-end frame, CPU baseline); the --no-* options drop single legs of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the frame of the last timed step (what rt_frame_download hands the caller) as "
+                         "DIR/rgb.npy, float32; over 64 MB a fixed seeded sample of its pixels")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-stats", action="store_true")
@@ -601,6 +682,8 @@ def main():
                     help="in-process multi-device run (no launcher): the HIP devices of the scene, e.g. 0,1,2,3 "
                          "(default 0..N-1 for --gpus N); repeats allowed to rehearse on one GPU (0,0)")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the headline frames only
+        a.no_cpu = a.no_stats = a.no_e2e = a.no_extra = a.no_side = a.no_cold = a.no_moving = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -707,7 +790,15 @@ def main():
                 "ms_per_step": round(el_c / a.steps * 1e3, 4), "steps": a.steps, "warmup": a.warmup, "prewarm_frames": 0,
                 "what": "the same timed frames measured first, right after the scene setup, with no prewarm (the GPU "
                         "leaving idle inside the window); `value` is the steady state after `prewarm_frames` frames"}
-    elapsed, st = timed_frames(rt, sc, cam, W, H, mode, shard, a.steps, a.warmup, barrier, sync_device, a.prewarm_ms)
+    elapsed, st = timed_frames(rt, sc, cam, W, H, mode, shard, a.steps, a.warmup, barrier, sync_device, a.prewarm_ms,
+                               enqueue=False)
+    # what the timed path computed in its last step: the frame the caller downloads (a rank under a launcher:
+    # the frame buffer with this rank's tiles filled in, one file set per rank)
+    dumped = None
+    if a.dump_outputs:
+        dumped = dump_arrays(a.dump_outputs, {"rgb": sc.download(W, H)}, suffix=f"_rank{rank}" if world > 1 else "")
+    if a.full:
+        st["enqueue_ms"] = enqueue_cost_ms(rt, sc, [cam] * min(a.steps, 3), W, H, mode, shard)
     my_rays = st["primary_rays"] * a.steps
     elapsed_max = reduce(elapsed, "MAX")
     total_rays = reduce(float(my_rays), "SUM")
@@ -726,8 +817,10 @@ def main():
                    for i, (k, r) in enumerate(zip(ks, rs))]
 
     # the dominant kernel's launch duration with one frame on the GPU (roofline denominator)
-    iso_ms, iso_trace_ms = isolated_kernel_ms(rt, sc, cam, W, H, mode, shard)
-    iso_ms_max = reduce(iso_ms, "MAX")
+    iso_ms = iso_trace_ms = iso_ms_max = None
+    if a.full:
+        iso_ms, iso_trace_ms = isolated_kernel_ms(rt, sc, cam, W, H, mode, shard)
+        iso_ms_max = reduce(iso_ms, "MAX")
 
     # the second frame size: N = 1 -> the C4 frame on this one GPU (strong-scaling base of C4);
     # N > 1 -> the metric's 1080p frame split over the N ranks
@@ -771,7 +864,9 @@ def main():
 
     # the headline frame's parity against the committed oracle digests (every pixel; N = 1, C3)
     headline_parity = None
-    if rank == 0 and n == 1 and not K and a.frame is None and a.scene == "soup" and a.tris == 1_000_000:
+    if not a.full:
+        pass
+    elif rank == 0 and n == 1 and not K and a.frame is None and a.scene == "soup" and a.tris == 1_000_000:
         headline_parity = frame_parity(rt, sc, W, H, mode, "C3" if a.mode == "primary" else "C3-full")
     elif devices and not K and a.frame is None and a.scene == "soup" and a.tris == 1_000_000 and a.mode == "primary":
         # the in-process multi-device C4 frame, assembled from every device's tiles, against the oracle's digests
@@ -844,10 +939,11 @@ def main():
                        # per-frame latency with frames in flight (first kernel start to last kernel end of one
                        # frame; frames overlap, so ms_per_step is the throughput interval) and alone
                        "kernel_ms_per_frame": round(kernel_ms_max, 4),
-                       "kernel_ms_one_frame_alone": round(iso_ms_max, 4),
-                       "host_enqueue_ms_per_frame": round(st.get("enqueue_ms", 0.0), 4),
+                       # (the lone frame, the enqueue cost and the tree's SAH cost: runs of their own, --full)
+                       "kernel_ms_one_frame_alone": round(iso_ms_max, 4) if iso_ms_max is not None else None,
+                       "host_enqueue_ms_per_frame": round(st["enqueue_ms"], 4) if "enqueue_ms" in st else None,
                        "bvh_nodes": info["bvh_nodes"], "bvh_depth": info["bvh_depth"],
-                       "bvh_sah_cost": {k: round(v, 3) for k, v in sc.tree_cost().items()},
+                       "bvh_sah_cost": {k: round(v, 3) for k, v in sc.tree_cost().items()} if a.full else None,
                        "wide_tree": {"nodes_per_copy": info["wide_nodes"], "depth": info["wide_depth"]} if info["wide_nodes"] else None,
                        "ref_boxes": info["n_ref_boxes"], "scene_setup_s": round(setup_s, 2),
                        "scene_setup_s_per_rank": [round(x, 2) for x in setup_per_rank],
@@ -860,7 +956,10 @@ def main():
             "roofline": roof,
             "cpu_baseline": cpu,
             "build": ident,
+            "full": a.full,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": a.dump_outputs, "files": dumped}
         if cold is not None:
             out["cold"] = cold
         if moving is not None:

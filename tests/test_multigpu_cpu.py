@@ -163,6 +163,97 @@ def test_bench_refuses_more_gpus_than_visible():
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr
 
 
+def test_dump_arrays_whole_and_sampled(tmp_path):
+    """bench.dump_arrays (--dump-outputs): a frame under the cap is written whole as float32; over the cap, the
+    same seeded sample of its pixels every time, with the pixels' indices, and the files together within the cap."""
+    H, W = 30, 44
+    rgb = np.arange(H * W * 3, dtype=np.float32).reshape(H, W, 3)
+    assert bench.DUMP_CAP_BYTES <= 64 * 1000 * 1000
+    assert bench.dump_arrays(str(tmp_path / "a"), {"rgb": rgb}) == {"rgb.npy": [H, W, 3]}
+    got = np.load(tmp_path / "a" / "rgb.npy")
+    assert got.dtype == np.float32 and got.tobytes() == rgb.tobytes()
+    cap = 4000
+    for d in ("b", "c"):
+        w = bench.dump_arrays(str(tmp_path / d), {"rgb": rgb}, cap=cap, suffix="_rank1")
+        assert sorted(w) == ["rgb_pixel_index_rank1.npy", "rgb_rank1.npy"]
+    idx, smp = np.load(tmp_path / "b" / "rgb_pixel_index_rank1.npy"), np.load(tmp_path / "b" / "rgb_rank1.npy")
+    assert idx.dtype == np.float64 and smp.dtype == np.float32 and smp.shape == (len(idx), 3)
+    assert idx.nbytes + smp.nbytes <= cap and len(idx) == cap // 20
+    assert (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < H * W
+    assert smp.tobytes() == rgb.reshape(-1, 3)[idx.astype(np.int64)].tobytes()
+    for f in w:
+        assert (tmp_path / "b" / f).read_bytes() == (tmp_path / "c" / f).read_bytes()
+
+
+def test_timed_frames_last_frame_is_the_last_timed_one():
+    """With enqueue=False (the headline run) timed_frames queues nothing after its timed frames, so the frame the
+    scene holds afterwards -- what --dump-outputs downloads -- is the last timed step's."""
+    class Scene:
+        def __init__(self):
+            self.queued, self.n = [], 0
+
+        def render_async(self, cam, *a, **k):
+            self.queued.append(cam)
+            self.n += 1
+
+        def synchronize(self):
+            self.n = 0
+            return {}
+
+        def synchronize_devices(self):
+            n, self.n = self.n, 0
+            return {"kernel_ms": 0.0, "launches": n, "primary_rays": 1}, []
+
+    class FakeRT:
+        DEFAULT_LIGHTS = []
+
+    for enqueue, extra in ((False, 0), (True, 3)):
+        sc = Scene()
+        _, st = bench.timed_frames(FakeRT, sc, "cam", 8, 8, 0, (0, 1), 5, 2, lambda: None, lambda: None,
+                                   enqueue=enqueue)
+        assert len(sc.queued) == 2 + 5 + extra and st["launches"] == 5
+        assert ("enqueue_ms" in st) == enqueue
+
+
+def test_timed_frames_any_number_of_steps():
+    """The library refuses more than 2048 renders between two synchronisations (rt_render_async); timed_frames
+    drains in between, so --steps and --warmup may be any number, and the chunks' read-outs add up to every
+    timed frame -- per device too."""
+    assert bench.MAX_PENDING_FRAMES == 2048
+
+    class Scene:  # two devices; 0.001 ms of kernel per frame
+        def __init__(self):
+            self.n = self.total = 0
+
+        def render_async(self, *a, **k):
+            if self.n >= 2048:
+                raise RuntimeError("more than 2048 renders without rt_synchronize")
+            self.n += 1
+            self.total += 1
+
+        def synchronize(self):
+            self.n = 0
+            return {}
+
+        def synchronize_devices(self):
+            n, self.n = self.n, 0
+            one = {"kernel_ms": 0.001 * n, "trace_kernel_ms": 0.0005 * n, "launches": n, "primary_rays": 50}
+            return dict(one, primary_rays=100), [dict(one), dict(one)]
+
+    class FakeRT:
+        DEFAULT_LIGHTS = []
+
+    for steps, warmup in ((2048, 2048), (2049, 2049), (5000, 4100)):
+        sc = Scene()
+        _, st = bench.timed_frames(FakeRT, sc, "cam", 8, 8, 0, (0, 1), steps, warmup, lambda: None,
+                                   lambda: __import__("time").sleep(0.002), enqueue=False)
+        assert sc.total == steps + warmup
+        assert st["launches"] == steps and st["primary_rays"] == 100
+        assert st["kernel_ms"] == pytest.approx(0.001 * steps) and st["trace_kernel_ms"] == pytest.approx(0.0005 * steps)
+        assert [p["launches"] for p in st["per_device"]] == [steps, steps]
+        assert [p["primary_rays"] for p in st["per_device"]] == [50, 50]
+
+
 def test_timed_window_must_hold_its_frames():
     """bench.timed_frames stops its clock after the caller's device synchronise and reads the frames' event times
     afterwards; a synchronise that drains nothing (the frames still running) must fail, not report the enqueue rate."""

@@ -7,7 +7,7 @@ OUT=gpurun_out/${TAG:-ab_libs}; mkdir -p $OUT
 for rep in $(seq 1 ${REPS:-2}); do
   for tag in ${LIBS:-default}; do
     if [ "$tag" = default ]; then lib=""; else lib="$PWD/ray-tracing-project_amd/lib/librtamd_$tag.so"; fi
-    RTAMD_LIB=$lib timeout -k 10 120 python bench.py --steps 20 --warmup 5 --no-cpu --no-side --no-extra ${BENCH_EXTRA:-} \
+    RTAMD_LIB=$lib timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-side --no-extra ${BENCH_EXTRA:-} \
         > $OUT/${tag}_r$rep.json 2> $OUT/${tag}_r$rep.err
     rc=$?
     python3 -c "

@@ -17,13 +17,31 @@ static int g_fail = 0;
     if (!(c)) { std::fprintf(stderr, "FAIL %s:%d %s\n", __FILE__, __LINE__, #c); g_fail++; } \
   } while (0)
 
+// A directory of this run's own under $TMPDIR (mkdtemp), removed with its files at the end of main: fixed
+// names in the shared directory collide with another user's (or an earlier run's) files there.
+static std::string g_tmp;
+static const char* const kTmpFiles[] = {"rt_asan_bad.obj", "rt_asan.rtscene", "rt_asan_bad.rtscene", "rt_asan.ppm",
+                                        "rt_asan8.ppm"};
+
 static std::string tmpdir() {
-  const char* t = std::getenv("TMPDIR");
-  return std::string(t ? t : "/tmp");
+  if (g_tmp.empty()) {
+    const char* t = std::getenv("TMPDIR");
+    std::string tmpl = std::string(t && *t ? t : "/tmp") + "/rt_asan_XXXXXX";
+    if (!mkdtemp(&tmpl[0])) { std::perror(("mkdtemp " + tmpl).c_str()); std::exit(2); }
+    g_tmp = tmpl;
+  }
+  return g_tmp;
+}
+
+static void remove_tmpdir() {
+  if (g_tmp.empty()) return;
+  for (const char* n : kTmpFiles) std::remove((g_tmp + "/" + n).c_str());
+  if (std::remove(g_tmp.c_str()) != 0) { std::perror(("remove " + g_tmp).c_str()); g_fail++; }
 }
 
 static void write_file(const std::string& p, const std::string& s) {
   FILE* f = std::fopen(p.c_str(), "wb");
+  if (!f) { std::perror(("fopen " + p).c_str()); std::exit(2); }
   std::fwrite(s.data(), 1, s.size(), f);
   std::fclose(f);
 }
@@ -156,6 +174,7 @@ int main(int argc, char** argv) {
   for (const char* n : {"cube.obj", "testding.obj", "dodgeColorTest.obj"})
     for (int bb : {RT_BOXES_HOST}) scene_roundtrip(scenes + "/" + n, bb);
   misc();
+  remove_tmpdir();
   std::printf("host_asan: %s (%d failed expectations)\n", g_fail ? "FAILED" : "ok", g_fail);
   return g_fail ? 1 : 0;
 }

@@ -17,10 +17,10 @@ for s in $STEPS; do
           --durations=15 > $OUT/pytest_gpu.log 2>&1
       rc=$?; echo "pytest rc=$rc"; tail -25 $OUT/pytest_gpu.log; hard $rc ;;
     bench)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; hard $rc; [ $rc -ne 0 ] && exit $rc ;;
     ploc)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
       rc=$?; echo "ploc rc=$rc"; cat $OUT/bench_ploc.json; hard $rc ;;
     profc2)
       OUTDIR=$OUT/profc2 \
@@ -33,7 +33,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in 24:0.7:0 32:0.7:0 16:0.7:0 24:0.5:0 24:1.0:0 24:0.7:1 32:0.5:1 24:1.0:1; do
         IFS=: read r tr ru <<< "$cfg"
-        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --steps 20 --warmup 5 \
+        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 \
             --builder ploc --no-cpu --no-side --no-extra > $OUT/ploc_$cfg.json 2> $OUT/ploc_$cfg.err
         rc=$?; echo "ploc $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/ploc_$cfg.json)"; hard $rc
       done ;;
@@ -42,7 +42,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in ${BUILDERS:-sbvh sah sahgpu sbvhgpu lbvh ploc:4}; do
         IFS=: read b r <<< "$cfg"
-        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
+        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
             --no-extra > $OUT/builder_$cfg.json 2> $OUT/builder_$cfg.err
         rc=$?; echo "builder $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/builder_$cfg.json)"; hard $rc
       done ;;

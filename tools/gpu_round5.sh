@@ -55,7 +55,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for k in none 256 512 1024 2048; do
           if [ $k = none ]; then envs=""; else envs="RT_SPLIT_KP_ANY=1 RT_SPLIT_KP=$k"; fi
-          env $envs timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
+          env $envs timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
               --frames-in-flight 1 > $OUT/c3split_${k}_r$rep.json 2> $OUT/c3split_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c3split $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c3split_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c3split $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'], d['roofline']['frac'], d['parity']['face_t_digest_equal'] if d.get('parity') else None)"
@@ -65,7 +65,7 @@ for s in $STEPS; do
     multi8)
       # eight replicas of the scene sharing the box's GPU: the in-process 8-device path end to end (enqueue workers,
       # assembly); the rate is one GPU's, the line shows the host enqueue cost per frame and per-device figures
-      timeout -k 10 300 python bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 --no-cpu \
+      timeout -k 10 300 python bench.py --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 --no-cpu \
           > $OUT/bench_multi8.json 2> $OUT/bench_multi8.err
       rc=$?; echo "multi8 rc=$rc"; cat $OUT/bench_multi8.json; hard $rc ;;
     fifsweep)
@@ -74,7 +74,7 @@ for s in $STEPS; do
         for sc in soup bunny; do
           md=primary; [ $sc = bunny ] && md=full
           for f in 1 2 3 4; do
-            timeout -k 10 120 python bench.py --scene $sc --mode $md --steps 20 --warmup 5 --no-cpu --no-side --no-extra \
+            timeout -k 10 120 python bench.py --full --scene $sc --mode $md --steps 20 --warmup 5 --no-cpu --no-side --no-extra \
                 --no-e2e --no-stats --frames-in-flight $f > $OUT/fif_${sc}_${f}_r$rep.json 2> $OUT/fif_${sc}_${f}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "fif $sc $f rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/fif_${sc}_${f}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('fif $sc f$f r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'], c['kernel_ms_one_frame_alone'])"
@@ -87,7 +87,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for c in 64 32 128 256; do
           for f in 4 1; do
-            RT_XCD_RUN=$c timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
+            RT_XCD_RUN=$c timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
                 --no-stats --frames-in-flight $f > $OUT/xcd_${c}_f${f}_r$rep.json 2> $OUT/xcd_${c}_f${f}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "xcd $c rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/xcd_${c}_f${f}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('xcd $c f$f r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -100,7 +100,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for rep in 1 2; do
         for k in ${C5K:-2048 1024 1536 3072}; do
-          RT_SPLIT_K=$k timeout -k 10 120 python bench.py --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
+          RT_SPLIT_K=$k timeout -k 10 120 python bench.py --full --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
               --no-extra --no-e2e --no-stats --frames-in-flight 1 > $OUT/c5split_${k}_r$rep.json 2> $OUT/c5split_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c5split $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c5split_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c5split $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -112,7 +112,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for rep in 1 2; do
         for v in $VALS; do
-          env $KNOB=$v timeout -k 10 120 python bench.py --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
+          env $KNOB=$v timeout -k 10 120 python bench.py --full --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
               --no-extra --no-e2e --no-stats --frames-in-flight ${FIF:-1} > $OUT/c5knob_${KNOB}_${v}_r$rep.json 2> $OUT/c5knob_${KNOB}_${v}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c5knob $KNOB=$v rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c5knob_${KNOB}_${v}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c5knob $KNOB=$v r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -123,7 +123,7 @@ for s in $STEPS; do
       # the timed-step count's effect on the C3 line (20 = the driver's), 4 frames in flight
       for rep in 1 2; do
         for k in 20 40 100; do
-          timeout -k 10 120 python bench.py --steps $k --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
+          timeout -k 10 120 python bench.py --full --steps $k --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
               > $OUT/steps_${k}_r$rep.json 2> $OUT/steps_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "steps $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/steps_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('steps $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'])"
@@ -134,7 +134,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for pw in 0 30 100 300; do
           for k in 20 100; do
-            timeout -k 10 120 python bench.py --steps $k --warmup 5 --prewarm-ms $pw --no-cpu --no-side --no-extra --no-e2e \
+            timeout -k 10 120 python bench.py --full --steps $k --warmup 5 --prewarm-ms $pw --no-cpu --no-side --no-extra --no-e2e \
                 --no-stats > $OUT/pw_${pw}_${k}_r$rep.json 2> $OUT/pw_${pw}_${k}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "prewarm $pw rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/pw_${pw}_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('prewarm $pw steps $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'])"
@@ -146,13 +146,13 @@ for s in $STEPS; do
       rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log; hard $rc; [ $rc -ne 0 ] && exit $rc ;;
     multi)
       # the in-process multi-device path (no launcher) with two replicas sharing the box's GPU
-      timeout -k 10 300 python bench.py --gpus 2 --devices 0,0 --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err
+      timeout -k 10 300 python bench.py --full --gpus 2 --devices 0,0 --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err
       rc=$?; echo "multi rc=$rc"; cat $OUT/bench_multi.json; hard $rc ;;
     bench)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; hard $rc; [ $rc -ne 0 ] && exit $rc ;;
     ploc)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
       rc=$?; echo "ploc rc=$rc"; cat $OUT/bench_ploc.json; hard $rc ;;
     profc2)
       OUTDIR=$OUT/profc2 \
@@ -165,7 +165,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in 24:0.7:0 32:0.7:0 16:0.7:0 24:0.5:0 24:1.0:0 24:0.7:1 32:0.5:1 24:1.0:1; do
         IFS=: read r tr ru <<< "$cfg"
-        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --steps 20 --warmup 5 \
+        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 \
             --builder ploc --no-cpu --no-side --no-extra > $OUT/ploc_$cfg.json 2> $OUT/ploc_$cfg.err
         rc=$?; echo "ploc $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/ploc_$cfg.json)"; hard $rc
       done ;;
@@ -174,7 +174,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in ${BUILDERS:-sbvh sah sahgpu sbvhgpu lbvh ploc:4}; do
         IFS=: read b r <<< "$cfg"
-        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
+        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
             --no-extra > $OUT/builder_$cfg.json 2> $OUT/builder_$cfg.err
         rc=$?; echo "builder $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/builder_$cfg.json)"; hard $rc
       done ;;

@@ -54,7 +54,7 @@ for s in $STEPS; do
         for d in 0,0 0,0,0,0,0,0,0,0; do
           n=$(echo $d | tr ',' ' ' | wc -w)
           for h in 0 1; do
-            RT_ASM_DEVICE=$h timeout -k 10 300 python bench.py --gpus $n --devices $d --steps 20 --warmup 5 --no-cpu --no-extra \
+            RT_ASM_DEVICE=$h timeout -k 10 300 python bench.py --full --gpus $n --devices $d --steps 20 --warmup 5 --no-cpu --no-extra \
                 > $OUT/asm_${n}_h${h}_r$rep.json 2> $OUT/asm_${n}_h${h}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "asm $n h$h rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/asm_${n}_h${h}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('asm n$n device$h r$rep', d['value'], d['ms_per_step'], c.get('e2e_frame_ms'), c.get('assembly_ms'), d.get('parity',{}).get('face_t_digest_equal'))"
@@ -70,14 +70,14 @@ for s in $STEPS; do
         for pool in ${SLOTQ_POOLS:-0 1}; do
           for n in 2 4; do
             RT_HWQ_GPU_CAP=${HWQCAP:-8} RT_SLOT_POOL=$pool BENCH_DEVICE=0 BENCH_BACKEND=gloo timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
-                --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n + 10 * pool)) bench.py --gpus $n \
+                --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n + 10 * pool)) bench.py --full --gpus $n \
                 --steps 20 --warmup 5 --no-cpu --no-e2e > $OUT/slotq_n${n}_p${pool}_r$rep.json 2> $OUT/slotq_n${n}_p${pool}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "slotq n$n pool$pool rc=$rc"; tail -5 $OUT/slotq_n${n}_p${pool}_r$rep.err; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/slotq_n${n}_p${pool}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('slotq n$n pool$pool r$rep', d['value'], d['ms_per_step'], [p['kernel_ms_per_frame'] for p in c['per_gpu']])"
           done
           for sc in soup:primary bunny:full; do
             IFS=: read scn md <<< "$sc"
-            RT_SLOT_POOL=$pool timeout -k 10 120 python bench.py --scene $scn --mode $md --steps 20 --warmup 5 --no-cpu --no-side \
+            RT_SLOT_POOL=$pool timeout -k 10 120 python bench.py --full --scene $scn --mode $md --steps 20 --warmup 5 --no-cpu --no-side \
                 --no-extra --no-e2e --no-stats --no-cold --no-moving > $OUT/slotq_1_${scn}_p${pool}_r$rep.json 2> $OUT/slotq_1_${scn}_p${pool}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "slotq 1 $scn rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/slotq_1_${scn}_p${pool}_r$rep.json').read().strip().splitlines()[-1]);print('slotq 1proc $scn pool$pool r$rep', d['value'], d['ms_per_step'])"
@@ -89,7 +89,7 @@ for s in $STEPS; do
       # the driver's 8-GPU launch rehearsed on the box's one GPU: torchrun 8 ranks (gloo timing reductions), the
       # scene built once by rank 0 and loaded by the others, cold + prewarmed C4 shards, e2e frame over gloo
       BENCH_DEVICE=0 BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-          --master-addr 127.0.0.1 --master-port 29788 bench.py --gpus 8 --steps 20 --warmup 5 --no-cpu \
+          --master-addr 127.0.0.1 --master-port 29788 bench.py --full --gpus 8 --steps 20 --warmup 5 --no-cpu \
           > $OUT/rehearse8.json 2> $OUT/rehearse8.err
       rc=$?; echo "rehearse8 rc=$rc"; cat $OUT/rehearse8.json; hard $rc ;;
     cli)
@@ -105,7 +105,7 @@ for s in $STEPS; do
           case $v in lib) envs="";; cap1000) envs="RT_HWQ_GPU_CAP=1000";; pool) envs="RT_SLOT_POOL=1";;
                      ss) envs="RT_SYNC_STREAMS=1";; sb) envs="RT_SORT_BEFORE=1";; both) envs="RT_SYNC_STREAMS=1 RT_SORT_BEFORE=1";;
                      r06a) envs="RTAMD_LIB=$PWD/ray-tracing-project_amd/lib/librtamd_r06a.so";; esac
-          env $envs timeout -k 10 120 python bench.py --scene bunny --mode primary --steps 40 --warmup 5 --no-cpu --no-side \
+          env $envs timeout -k 10 120 python bench.py --full --scene bunny --mode primary --steps 40 --warmup 5 --no-cpu --no-side \
               --no-extra --no-e2e --no-stats --no-cold --no-moving > $OUT/c2diag_${v}_r$rep.json 2> $OUT/c2diag_${v}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c2diag $v rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c2diag_${v}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c2diag $v r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'], c['kernel_ms_per_frame'])"
@@ -140,7 +140,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for k in none 256 512 1024 2048; do
           if [ $k = none ]; then envs=""; else envs="RT_SPLIT_KP_ANY=1 RT_SPLIT_KP=$k"; fi
-          env $envs timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
+          env $envs timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
               --frames-in-flight 1 > $OUT/c3split_${k}_r$rep.json 2> $OUT/c3split_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c3split $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c3split_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c3split $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'], d['roofline']['frac'], d['parity']['face_t_digest_equal'] if d.get('parity') else None)"
@@ -161,7 +161,7 @@ for s in $STEPS; do
     multi8)
       # eight replicas of the scene sharing the box's GPU: the in-process 8-device path end to end (enqueue workers,
       # assembly); the rate is one GPU's, the line shows the host enqueue cost per frame and per-device figures
-      timeout -k 10 300 python bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 --no-cpu \
+      timeout -k 10 300 python bench.py --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 20 --warmup 5 --no-cpu \
           > $OUT/bench_multi8.json 2> $OUT/bench_multi8.err
       rc=$?; echo "multi8 rc=$rc"; cat $OUT/bench_multi8.json; hard $rc ;;
     fifsweep)
@@ -170,7 +170,7 @@ for s in $STEPS; do
         for sc in soup bunny; do
           md=primary; [ $sc = bunny ] && md=full
           for f in 1 2 3 4; do
-            timeout -k 10 120 python bench.py --scene $sc --mode $md --steps 20 --warmup 5 --no-cpu --no-side --no-extra \
+            timeout -k 10 120 python bench.py --full --scene $sc --mode $md --steps 20 --warmup 5 --no-cpu --no-side --no-extra \
                 --no-e2e --no-stats --frames-in-flight $f > $OUT/fif_${sc}_${f}_r$rep.json 2> $OUT/fif_${sc}_${f}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "fif $sc $f rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/fif_${sc}_${f}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('fif $sc f$f r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'], c['kernel_ms_one_frame_alone'])"
@@ -183,7 +183,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for c in 64 32 128 256; do
           for f in 4 1; do
-            RT_XCD_RUN=$c timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
+            RT_XCD_RUN=$c timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e \
                 --no-stats --frames-in-flight $f > $OUT/xcd_${c}_f${f}_r$rep.json 2> $OUT/xcd_${c}_f${f}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "xcd $c rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/xcd_${c}_f${f}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('xcd $c f$f r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -196,7 +196,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for rep in 1 2; do
         for k in ${C5K:-2048 1024 1536 3072}; do
-          RT_SPLIT_K=$k timeout -k 10 120 python bench.py --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
+          RT_SPLIT_K=$k timeout -k 10 120 python bench.py --full --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
               --no-extra --no-e2e --no-stats --frames-in-flight 1 > $OUT/c5split_${k}_r$rep.json 2> $OUT/c5split_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c5split $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c5split_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c5split $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -208,7 +208,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for rep in 1 2; do
         for v in $VALS; do
-          env $KNOB=$v timeout -k 10 120 python bench.py --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
+          env $KNOB=$v timeout -k 10 120 python bench.py --full --scene bunny --mode full --steps 40 --warmup 5 --no-cpu --no-side \
               --no-extra --no-e2e --no-stats --frames-in-flight ${FIF:-1} > $OUT/c5knob_${KNOB}_${v}_r$rep.json 2> $OUT/c5knob_${KNOB}_${v}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "c5knob $KNOB=$v rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/c5knob_${KNOB}_${v}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('c5knob $KNOB=$v r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
@@ -219,7 +219,7 @@ for s in $STEPS; do
       # the timed-step count's effect on the C3 line (20 = the driver's), 4 frames in flight
       for rep in 1 2; do
         for k in 20 40 100; do
-          timeout -k 10 120 python bench.py --steps $k --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
+          timeout -k 10 120 python bench.py --full --steps $k --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
               > $OUT/steps_${k}_r$rep.json 2> $OUT/steps_${k}_r$rep.err
           rc=$?; [ $rc -ne 0 ] && { echo "steps $k rc=$rc"; hard $rc; exit $rc; }
           python3 -c "import json;d=json.loads(open('$OUT/steps_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('steps $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'])"
@@ -230,7 +230,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for pw in 0 30 100 300; do
           for k in 20 100; do
-            timeout -k 10 120 python bench.py --steps $k --warmup 5 --prewarm-ms $pw --no-cpu --no-side --no-extra --no-e2e \
+            timeout -k 10 120 python bench.py --full --steps $k --warmup 5 --prewarm-ms $pw --no-cpu --no-side --no-extra --no-e2e \
                 --no-stats > $OUT/pw_${pw}_${k}_r$rep.json 2> $OUT/pw_${pw}_${k}_r$rep.err
             rc=$?; [ $rc -ne 0 ] && { echo "prewarm $pw rc=$rc"; hard $rc; exit $rc; }
             python3 -c "import json;d=json.loads(open('$OUT/pw_${pw}_${k}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('prewarm $pw steps $k r$rep', d['value'], d['ms_per_step'], c['kernel_ms_per_frame'])"
@@ -242,13 +242,13 @@ for s in $STEPS; do
       rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log; hard $rc; [ $rc -ne 0 ] && exit $rc ;;
     multi)
       # the in-process multi-device path (no launcher) with two replicas sharing the box's GPU
-      timeout -k 10 300 python bench.py --gpus 2 --devices 0,0 --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err
+      timeout -k 10 300 python bench.py --full --gpus 2 --devices 0,0 --steps 20 --warmup 5 > $OUT/bench_multi.json 2> $OUT/bench_multi.err
       rc=$?; echo "multi rc=$rc"; cat $OUT/bench_multi.json; hard $rc ;;
     bench)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json; hard $rc; [ $rc -ne 0 ] && exit $rc ;;
     ploc)
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
+      timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --builder ploc --no-cpu --no-side > $OUT/bench_ploc.json 2> $OUT/bench_ploc.err
       rc=$?; echo "ploc rc=$rc"; cat $OUT/bench_ploc.json; hard $rc ;;
     profc2)
       OUTDIR=$OUT/profc2 \
@@ -261,7 +261,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in 24:0.7:0 32:0.7:0 16:0.7:0 24:0.5:0 24:1.0:0 24:0.7:1 32:0.5:1 24:1.0:1; do
         IFS=: read r tr ru <<< "$cfg"
-        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --steps 20 --warmup 5 \
+        RT_PLOC_RADIUS=$r RT_PLOC_TRAV=$tr RT_PLOC_RULE=$ru timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 \
             --builder ploc --no-cpu --no-side --no-extra > $OUT/ploc_$cfg.json 2> $OUT/ploc_$cfg.err
         rc=$?; echo "ploc $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/ploc_$cfg.json)"; hard $rc
       done ;;
@@ -270,7 +270,7 @@ for s in $STEPS; do
       export RTAMD_DEBUG_KNOBS=1
       for cfg in ${BUILDERS:-sbvh sah sahgpu sbvhgpu lbvh ploc:4}; do
         IFS=: read b r <<< "$cfg"
-        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
+        RT_PLOC_RADIUS=${r:-24} timeout -k 10 120 python bench.py --full --steps 20 --warmup 5 --builder $b --no-cpu --no-side \
             --no-extra > $OUT/builder_$cfg.json 2> $OUT/builder_$cfg.err
         rc=$?; echo "builder $cfg rc=$rc $(python3 tools/ploc_line.py $OUT/builder_$cfg.json)"; hard $rc
       done ;;

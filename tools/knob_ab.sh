@@ -14,7 +14,7 @@ for cfg in ${CFGS:-soup:primary:1 soup:primary:4}; do
   for v in $VALS; do
     out=gpurun_out/$TAG/${v}_${scene}_${mode}_f${fif}_r$rep.json
     if [ "$v" = none ]; then envs=""; else envs="$KNOB=$v"; fi
-    env $envs timeout -k 10 300 python bench.py --scene $scene --mode $mode --frames-in-flight $fif --steps ${STEPS:-40} \
+    env $envs timeout -k 10 300 python bench.py --full --scene $scene --mode $mode --frames-in-flight $fif --steps ${STEPS:-40} \
         --warmup 5 --no-cpu --no-stats --no-e2e --no-extra --no-side ${BENCH_EXTRA:-} > $out 2> ${out%.json}.err
     rc=$?
     python3 -c "import json; d=json.loads(open('$out').read().strip().splitlines()[-1]); print('$KNOB=$v $scene $mode fif$fif r$rep', d['value'], d['ms_per_step'], d['config']['kernel_ms_one_frame_alone'])" 2>/dev/null || echo "$v rc=$rc"

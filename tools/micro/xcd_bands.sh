@@ -8,7 +8,7 @@ OUT=gpurun_out/xcdbands; mkdir -p $OUT
 for rep in 1 2; do
   for c in ${RUNS:-64 510 1020 2040 4080}; do
     for f in 4 1; do
-      RT_XCD_RUN=$c timeout -k 10 120 python bench.py --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
+      RT_XCD_RUN=$c timeout -k 10 120 python bench.py --full --steps 40 --warmup 5 --no-cpu --no-side --no-extra --no-e2e --no-stats \
           --frames-in-flight $f > $OUT/c${c}_f${f}_r$rep.json 2> $OUT/c${c}_f${f}_r$rep.err || exit 1
       python3 -c "import json;d=json.loads(open('$OUT/c${c}_f${f}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('run $c fif $f r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'])"
     done
@@ -16,5 +16,5 @@ for rep in 1 2; do
 done
 for c in ${PMC_RUNS:-64 4080}; do
   RT_XCD_RUN=$c timeout -s KILL 120 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d $OUT/pmc_c$c -o run --output-format csv -- \
-      python bench.py --steps 10 --warmup 2 --no-cpu --no-side --no-extra --no-e2e --no-stats > $OUT/pmc_c$c.log 2>&1 || exit 1
+      python bench.py --full --steps 10 --warmup 2 --no-cpu --no-side --no-extra --no-e2e --no-stats > $OUT/pmc_c$c.log 2>&1 || exit 1
 done

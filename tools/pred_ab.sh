@@ -17,7 +17,7 @@ for rep in 1 2; do
     if [ $lib = cur ]; then L=$PWD/ray-tracing-project_amd/lib/librtamd.so; else L=$PWD/ray-tracing-project_amd/lib/librtamd_$lib.so; fi
     for sc in soup:primary bunny:full; do
       IFS=: read scn md <<< "$sc"
-      RTAMD_LIB=$L timeout -k 10 120 python bench.py --scene $scn --mode $md --steps 40 --warmup 5 --no-cpu --no-side --no-extra \
+      RTAMD_LIB=$L timeout -k 10 120 python bench.py --full --scene $scn --mode $md --steps 40 --warmup 5 --no-cpu --no-side --no-extra \
           --no-e2e --no-stats --no-cold --no-moving > $OUT/static_${lib}_${scn}_r$rep.json 2> $OUT/static_${lib}_${scn}_r$rep.err
       rc=$?; [ $rc -ne 0 ] && { echo "static $lib $scn rc=$rc"; tail -3 $OUT/static_${lib}_${scn}_r$rep.err; exit $rc; }
       python3 -c "import json;d=json.loads(open('$OUT/static_${lib}_${scn}_r$rep.json').read().strip().splitlines()[-1]);c=d['config'];print('static $lib $scn r$rep', d['value'], d['ms_per_step'], c['kernel_ms_one_frame_alone'], d['roofline']['kernel_ms_isolated'])"

@@ -14,7 +14,7 @@ timeout -k 10 120 rocprofv3 -L > $OUT/counters_avail.txt 2>&1 || true
 timeout -k 10 120 python3 tools/kernel_clock.py $OUT/kernel_clock.json $ARGS > $OUT/kernel_clock.log 2>&1
 rc=$?; echo "kernel clock rc=$rc"; case $rc in 124|134|137|139) exit $rc;; esac
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv -- \
-    python3 bench.py $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err
+    python3 bench.py --full $ARGS > $OUT/trace_bench.json 2> $OUT/trace.err
 rc=$?; echo "trace rc=$rc"; [ $rc -ne 0 ] && exit $rc
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES" \
@@ -23,7 +23,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ
            ${EXTRA_PMC:-}; do
   i=$((i+1))
   timeout -k 10 300 rocprofv3 --pmc $set -d $OUT/pmc$i -o run --output-format csv -- \
-      python3 bench.py ${PMC_ARGS:---steps 5 --warmup 1 --no-cpu --no-stats --no-extra --no-e2e --no-side --frames-in-flight 1} > $OUT/pmc$i.json 2> $OUT/pmc$i.err
+      python3 bench.py --full ${PMC_ARGS:---steps 5 --warmup 1 --no-cpu --no-stats --no-extra --no-e2e --no-side --frames-in-flight 1} > $OUT/pmc$i.json 2> $OUT/pmc$i.err
   rc=$?; echo "pmc$i ($set) rc=$rc"
   case $rc in 124|134|137|139) exit $rc;; esac
 done
