@@ -280,7 +280,9 @@ typedef struct rt_frame {
 #define RT_FRAME_TIMELINE 4   /* diagnostics: each wave of the render kernel records its start / end clocks
                                  and the CU it ran on (rt_debug_timeline); PRIMARY and FULL kernels */
 #define RT_FRAME_WAVE_STATS 8 /* diagnostics, with RT_FRAME_STATS: each wave of the counting run also records its own
-                                 counts (rt_debug_wave_stats) */
+                                 counts (rt_debug_wave_stats). Only at the mode's own recursion limit (max_depth 0,
+                                 or 1 for PRIMARY / 2 for FULL): with any other max_depth the frame is refused
+                                 with RT_ERR_UNSUPPORTED, the generic-depth kernel keeps no per-wave counts */
 
 typedef struct rt_stats {
   double kernel_ms;         /* device time of the render kernels since the previous rt_synchronize,

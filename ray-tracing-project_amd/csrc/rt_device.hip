@@ -1260,6 +1260,13 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
     s->last_timeline_waves = (int64_t)waves;
   }
   if (stats && (fr->flags & RT_FRAME_WAVE_STATS)) {  // per logical wave (tile * 4 + quarter)
+    // the generic traceRay kernel (k_render_depth: any recursion limit but the mode's own, or variant 65536)
+    // writes no per-wave records: refuse the frame instead of returning all-zero records
+    const int own_depth = fr->mode == RT_MODE_FULL ? 2 : 1;
+    if (!boxcol && ((fr->max_depth > 0 && fr->max_depth != own_depth) || (variant & 65536))) {
+      set_error("rt_render: RT_FRAME_WAVE_STATS needs the mode's own max_depth (the generic-depth kernel keeps no per-wave counts)");
+      return RT_ERR_UNSUPPORTED;
+    }
     const size_t lw = (size_t)grid * 4;
     if (lw > slot.wave_stats_waves) {
       HIPCHECK(hipStreamSynchronize(st));

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, scene_path
-from test_oracle_pinning import read_kat, same_bits
+from test_oracle_pinning import colour_errors, read_kat, same_bits
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -26,11 +26,10 @@ def compare(rgb, face, t, orgb, oface, ot, what):
     oface = np.asarray(oface).reshape(-1)
     nbad_face = int((face != oface).sum())
     tb = same_bits(np.asarray(t).reshape(-1), np.asarray(ot).reshape(-1))
-    err = np.abs(np.asarray(rgb, np.float64).reshape(-1, 3) - np.asarray(orgb, np.float64).reshape(-1, 3))
-    err = np.where(np.isnan(err) & np.isnan(np.asarray(rgb).reshape(-1, 3)) & np.isnan(np.asarray(orgb).reshape(-1, 3)), 0, err)
-    linf = float(np.nanmax(err)) if err.size else 0.0
+    odd, linf = colour_errors(np.asarray(rgb).reshape(-1, 3), np.asarray(orgb).reshape(-1, 3))
     assert nbad_face == 0, f"{what}: {nbad_face} pixels hit a different face"
     assert tb.all(), f"{what}: {int((~tb).sum())} pixels differ in t bits"
+    assert odd == 0, f"{what}: {odd} colour values are NaN or infinite on one side only"
     assert linf < TOL, f"{what}: colour L_inf {linf:.3g} >= {TOL}"
     return linf
 
@@ -203,19 +202,21 @@ def test_stats_counting_run(rt, soup):
 
 # variant bits the product library serves itself (rt_api.h rt_debug_set_variant)
 VARIANTS = {"xcd-order": 4, "xcd-runs-4": 512, "dispatch-order": 1536, "full-8-waves": 8192, "full-small-build": 16384,
-            "split-primary": 32768, "generic-depth-kernel": 65536}
+            "split-primary": 32768, "generic-depth-kernel": 65536, "coarse-cost-buckets": 262144,
+            "primary-binary-tree": 2097152}
 # the A/B kernels of the variants library only (rt_variants.hip, `make variants`)
 VARIANTS_LIB = {"vgpr-stack": 1, "wide4": 2, "full-pipeline": 16, "pipeline-lane-refl": 48,
                 "pipeline-lane-all": 16 | 32 | 64 | 128, "two-rays-per-lane": 256, "persistent": 2048,
                 "persistent-no-steal": 2048 | 4096, "dual-chain": 1048576}
 
 
-def variant_frames_identical(rt, scenes, bits):
+def variant_frames_identical(rt, scenes, bits, extra=()):
     """Render bunny (PRIMARY + FULL, 1080p) and the 1M soup (FULL 640x360, PRIMARY 1000x563) with the default
-    kernels and with kernel variant `bits`; returns the cases whose rgb / face / t differ."""
+    kernels and with kernel variant `bits`; returns the cases whose rgb / face / t differ. extra: further
+    (scene, W, H, mode) cases."""
     bunny, soup = scenes
     cases = [(bunny, 1920, 1080, rt.RT_MODE_PRIMARY), (bunny, 1920, 1080, rt.RT_MODE_FULL),
-             (soup, 640, 360, rt.RT_MODE_FULL), (soup, 1000, 563, rt.RT_MODE_PRIMARY)]
+             (soup, 640, 360, rt.RT_MODE_FULL), (soup, 1000, 563, rt.RT_MODE_PRIMARY)] + list(extra)
     bad = []
     for sc, W, H, m in cases:
         cam = rt.flycam(W, H, 0, 0, 20)
@@ -646,6 +647,22 @@ def test_wave_stats_sum_to_frame_counters(rt):
     assert [int(ws[:, p].sum()) for p in range(4)] == c[ST_PS:ST_PS + 4]
     assert [int(ws[:, 4 + p].sum()) for p in range(4)] == c[ST_PT:ST_PT + 4]
     assert c[ST_PS] > 0 and c[ST_PS + 2] > 0  # primary and reflection walks happened
+    # the generic-depth kernel (any max_depth but the mode's own) keeps no per-wave counts: such a frame is
+    # refused, and no record can be read after it -- never RT_OK with all-zero records
+    for mode in (rt.RT_MODE_FULL, rt.RT_MODE_PRIMARY):
+        with pytest.raises(rt.RTError, match="RT_FRAME_WAVE_STATS"):
+            sc.render(cam, rt.DEFAULT_LIGHTS, W, H, mode=mode, max_depth=3,
+                      flags=rt.RT_FRAME_STATS | rt.RT_FRAME_WAVE_STATS)
+        # the same frame without the per-wave flag still counts, and leaves no per-wave record behind
+        st3 = sc.render(cam, rt.DEFAULT_LIGHTS, W, H, mode=mode, max_depth=3, flags=rt.RT_FRAME_STATS)[1]
+        assert st3["primary_rays"] == W * H
+        with pytest.raises(rt.RTError):
+            sc.wave_stats()
+    # the mode's own depth given explicitly is the tuned kernel: records as above
+    sc.render(cam, rt.DEFAULT_LIGHTS, W, H, mode=rt.RT_MODE_FULL, max_depth=2,
+              flags=rt.RT_FRAME_STATS | rt.RT_FRAME_WAVE_STATS)
+    ws2 = sc.wave_stats().astype(np.int64)
+    assert len(ws2) == len(ws) and [int(ws2[:, p].sum()) for p in range(4)] == c[ST_PS:ST_PS + 4]
     with pytest.raises(rt.RTError):  # a frame without the flag has no per-wave record
         sc.render(cam, rt.DEFAULT_LIGHTS, W, H)
         sc.wave_stats()

@@ -61,6 +61,18 @@ def same_bits(a, b):
     return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
 
 
+def colour_errors(a, b):
+    """(positions whose NaN / +inf / -inf class differs between a and b, L_inf over the positions finite in
+    both). The GPU parity helpers assert the first is 0 before they look at the second: a colour that is NaN
+    or infinite on one side only is a mismatch, never a pixel dropped from the maximum."""
+    a = np.asarray(a, np.float64)
+    b = np.asarray(b, np.float64).reshape(a.shape)
+    odd = (np.isnan(a) != np.isnan(b)) | (np.isposinf(a) != np.isposinf(b)) | (np.isneginf(a) != np.isneginf(b))
+    fin = np.isfinite(a) & np.isfinite(b)
+    err = np.abs(np.where(fin, a, 0.0) - np.where(fin, b, 0.0))
+    return int(odd.sum()), (float(err.max()) if err.size else 0.0)
+
+
 @pytest.mark.parametrize("sec", read_kat(), ids=lambda s: f"op{s[0]}")
 def test_oracle_eigen_primitives_bit_exact(orc, sec):
     op, n, il, ol, inp, exp = sec

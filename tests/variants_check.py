@@ -1,7 +1,8 @@
 """Child process of test_variants_library_renders_identical_bits (tests/test_gpu_parity.py): loads the
 library named by RTAMD_LIB (lib/librtamd_variants.so: the product kernels plus the A/B kernels of
 rt_variants.hip) and renders, for every A/B variant, bunny (PRIMARY + FULL, 1080p) and the 1M soup (FULL
-640x360, PRIMARY 1000x563) with the default kernels and with the variant. Prints one JSON line:
+640x360, PRIMARY 1000x563) and the 64x40 frame of the tie scene (tests/edge_scenes.py: three faces at
+bit-identical t under every pixel; PRIMARY + FULL) with the default kernels and with the variant. Prints one JSON line:
 {variant name: [differing cases]}. Not a test module (no test_ functions); needs a GPU."""
 import json
 import os
@@ -11,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
 import conftest  # noqa: E402  (loads ray-tracing-project_amd/rtamd.py, honouring RTAMD_LIB)
+import edge_scenes  # noqa: E402
 from conftest import scene_path  # noqa: E402
 from test_gpu_parity import VARIANTS_LIB, variant_frames_identical  # noqa: E402
 
@@ -23,9 +25,12 @@ def main():
     bunny = rt.Scene(rt.Mesh.load_obj(scene_path("bunny.obj")), builder=rt.RT_BUILDER_SBVH)
     mesh, _, _ = rt.soup_mesh(1_000_000)
     soup = rt.Scene(mesh, builder=rt.RT_BUILDER_SBVH)
+    (v, f, m, g), _ = edge_scenes.tie_scene()
+    tie = rt.Scene(rt.Mesh.from_arrays(v, f, m, groups=g), builder=rt.RT_BUILDER_SBVH, min_faces=8)
+    extra = [(tie, 64, 40, rt.RT_MODE_PRIMARY), (tie, 64, 40, rt.RT_MODE_FULL)]
     out = {}
     for name, bits in sorted(VARIANTS_LIB.items()):
-        out[name] = [list(map(int, c)) for c in variant_frames_identical(rt, (bunny, soup), bits)]
+        out[name] = [list(map(int, c)) for c in variant_frames_identical(rt, (bunny, soup), bits, extra)]
         print(f"{name}: {'identical' if not out[name] else out[name]}", file=sys.stderr, flush=True)
     # the FULL stage pipeline (variant 16) sizes its ray lists for whole frames: a sharded frame is refused
     # with an error, never rendered wrong
