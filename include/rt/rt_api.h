@@ -421,6 +421,20 @@ int rt_debug_tree_cost(const rt_scene* s, double k_trav, double out[4]);
  * (0: records exceed 4 GiB), out[1] = byte offset of the wide copies (0: the wide tree is dropped because
  * a wide record offset would reach 2^31, the leaf-handle bit). */
 int rt_debug_record_layout(int64_t n_nodes, int64_t n_tris, int64_t n_wide, int64_t out[2]);
+/* The dispatch plan of a frame (host only, no device; csrc/rt_dispatch.h plan_frame, which rt_render reads for
+ * every kernel and block-order decision), with the dispatch knobs at their defaults.
+ * in[0..10] (n_in = 11): mode, max_depth, flags, tiles_x, tiles_y (16x16-pixel tiles of the frame), shard_index,
+ * shard_count (>= 1), kernel variant, bytes of the scene's binary node + triangle records, whether the scene has
+ * the quantised 4-wide tree, whether no other frame of the scene is in flight.
+ * out[0..13] (n_out = 14): 0 kernel (0 none: empty shard, 1 generic depth, 2 PRIMARY fused, 3 PRIMARY trace +
+ * shade, 4 PRIMARY dual, 5 PRIMARY two rays per lane, 6 PRIMARY persistent, 7 FULL megakernel, 8 FULL pipeline),
+ * 1 traversal flavour (0 VGPR stack, 1 LDS stack, 2 quantised 4-wide), 2 needs the variants library, 3 the
+ * shard's tile slots, 4 units (one-wave blocks of the render kernel), 5 recursion limit, 6 L2-resident scene,
+ * 7 xcd_remap (run length of the chunked XCD block order; 1 contiguous per XCD, 0 plain), 8 the kernel writes
+ * per-wave counts (else RT_FRAME_WAVE_STATS is refused), 9 dispatched longest-first, 10 ceiling of the waves
+ * split into sub-waves once the frame has an order, 11 takes the next XCD band rotation, 12 binds the stage
+ * pipeline's buffers (whole frames only), 13 FULL megakernel's small-scene build. */
+int rt_debug_frame_plan(const int64_t in[], int32_t n_in, int32_t out[], int32_t n_out);
 /* The accept path's shortcuts (host data, no device needed): counts[0] = triangle records, counts[1] =
  * those whose interpolated normal is certified non-zero, counts[2] = those with a reference-box
  * certificate; *cert_origin_max (may be NULL) = the object-space origin range (max norm) within which
@@ -431,7 +445,9 @@ int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origi
 /* Kernel-variant override (tests and A/B measurements only; default 0 = the measured-best kernels).
  * Bits of the product library: 4 / 512 / 1536 tile orders, 8192 / 16384 FULL megakernel builds, 32768
  * PRIMARY as trace + shade kernels, 65536 the generic traceRay kernel, 131072 / 262144 / 524288
- * longest-first dispatch knobs, 2097152 PRIMARY packets on the binary tree. Bits of the variants library
+ * longest-first dispatch knobs (524288, longest-first also with frames in flight, is A/B only: the frames share
+ * one order, which one of them may read while another's sort rewrites it, and then skip or repeat waves),
+ * 2097152 PRIMARY packets on the binary tree. Bits of the variants library
  * only (make variants -> librtamd_variants.so; the product library's rt_render returns
  * RT_ERR_UNSUPPORTED for them): 1 VGPR wave stack, 2 4-wide quantised BVH (scenes of the host builders,
  * which also build that tree), 16 FULL as a stage pipeline (whole frames only: a sharded frame returns
@@ -441,8 +457,8 @@ int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origi
  * variant renders the same bits. Returns the previous value. */
 int rt_debug_set_variant(int32_t v);
 /* Diagnostics: on = 1 lets the library read its A/B and diagnostic environment knobs (RT_KERNEL_VARIANT,
- * RT_SPLIT_K, RT_SPLIT_KP, RT_SPLIT_KP_ANY, RT_TIMELINE_SPLIT, RT_XCD_RUN, RT_LDS_PAD, RT_LPT_REFRESH, RT_LPT_MOVED,
- * RT_LPT_DILATE, RT_LPT_PRED, RT_LPT_DILW, RT_ASM_DEVICE, RT_SLOT_POOL, RT_HWQ_GPU_CAP, RT_SAH_TRAV, RT_SBVH_BUDGET, RT_NODE_LAYOUT, RT_PLOC_RADIUS, RT_PLOC_TRAV, RT_PLOC_RULE, RT_TIMING); by default
+ * RT_SPLIT_K, RT_SPLIT_KP, RT_TIMELINE_SPLIT, RT_LDS_PAD, RT_LPT_REFRESH, RT_LPT_MOVED,
+ * RT_LPT_DILATE, RT_LPT_PRED, RT_ASM_DEVICE, RT_SLOT_POOL, RT_HWQ_GPU_CAP, RT_SAH_TRAV, RT_SBVH_BUDGET, RT_NODE_LAYOUT, RT_PLOC_RADIUS, RT_PLOC_TRAV, RT_PLOC_RULE, RT_TIMING); by default
  * (and after on = 0) it ignores the process environment, so a drop-in's trees, kernels and dispatch never
  * depend on it. Turning it on also takes RT_KERNEL_VARIANT as the current kernel variant. */
 int rt_debug_env_knobs(int32_t on);

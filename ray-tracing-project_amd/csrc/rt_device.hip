@@ -19,6 +19,7 @@
 #include <thread>
 #include <vector>
 
+#include "rt_dispatch.h"
 #include "rt_kernels.h"
 
 namespace rt {
@@ -71,11 +72,6 @@ static void camera_step(const float* vp_prev, const float* v_cur, float* step3) 
     step3[i] = (float)m;
   }
 }
-constexpr int kSplitK = 1536;  // FULL lone frames: waves split into 16-lane sub-waves (FrameParams::split_k); round 5
-                               // re-sweep without the spill: 1536 +2.5..6% over 2048 (profiles/ab/r05_c5_split_ab.txt)
-constexpr int kSplitKPrimary = 256;   // the same for k_primary_fused (small scenes); round 6 re-sweep after the
-                                      // scene-level map: 256 against 1024 -2.5% static, -7% moving, -8% at a stopped
-                                      // pose (C2 lone frames, profiles/ab/r06_split_size_ab.txt)
 __device__ __forceinline__ uint32_t lpt_bucket(uint32_t c, int shift) {
   // 4 buckets per octave: exponent and 2 mantissa bits of (float)c; costs of 2^10 .. 2^18 shader cycles
   // (0.5 .. 120 us at 2.1 GHz) spread over the buckets, longest first (bucket 0)
@@ -1002,52 +998,6 @@ static int ensure_fb(rt_scene::FrameSlot& f, size_t npix) {
   return RT_OK;
 }
 
-// variant bits (debug knob RT_KERNEL_VARIANT, for A/B measurements; 0 = the measured-best default):
-// 1 = binary nodes + lane-register (VGPR) stack, 2 = 4-wide quantised nodes (when the scene has
-// them), 4 = XCD-contiguous tile order, 512 / 1024 / 1536 = block runs of 4 / 16 / plain dispatch order
-// instead of the default 64-block runs per XCD, 16 = FULL as the stage pipeline (k_full_*) instead of one
-// kernel; with 16: 32 / 64 / 128 = per-lane traversal for the reflection rays / the shadow rays of
-// reflection hits / the shadow rays of primary hits; 256 = two rays per lane (PRIMARY), 2048 =
-// persistent-threads PRIMARY traversal with per-XCD work counters (4096: without stealing); 32768 =
-// PRIMARY as trace + shade kernels instead of the fused k_primary_fused; 8192 /
-// 16384 = the FULL megakernel's 8-wave / small-scene (6-wave) build regardless of the scene size;
-// 65536 = the generic traceRay kernel (k_render_depth) also at the modes' own depths; 131072 = the
-// default chunked-XCD dispatch order instead of longest-first (k_order_lpt); 262144 = longest-first
-// with half as many cost buckets (2 per octave: coarser, more spatial order kept); 524288 = longest-first
-// also while other frames are in flight; 2097152 = PRIMARY packets on the binary tree instead of the fp32
-// 4-wide tree (traverse_wide_fast).
-// Default: binary nodes + LDS stack, FULL as one kernel (k_render_full) at the occupancy its scene
-// size selects.
-static int pick_trav(const FrameParams& P, int variant) {
-  if (variant & 1) return TRAV_B2_VGPR;
-  if ((variant & 2) && P.sc.n_nodes4 > 0) return TRAV_W4;
-  return TRAV_B2_LDS;
-}
-// The product's traversal flavour is the binary tree with the LDS wave stack (TRAV_B2_LDS); the other
-// flavours are A/B variants built only into the variants library (variant_launch).
-template <bool STATS>
-static void launch_trace(const FrameParams& P, int grid, hipStream_t st, int trav) {
-  if (trav != TRAV_B2_LDS) {
-    VariantCall c;
-    c.P = P, c.grid = grid, c.st = st, c.trav = trav, c.stats = STATS;
-    variant_launch(VOP_TRACE_PRIMARY, c);
-    return;
-  }
-  hipLaunchKernelGGL((k_trace_primary<STATS, TRAV_B2_LDS>), dim3(grid * (4 / kTraceWPB)), dim3(64 * kTraceWPB), 0, st, P);
-}
-template <bool STATS, bool HITS>
-static void launch_full(const FrameParams& P, int grid, hipStream_t st, int trav, bool small) {
-  if (trav != TRAV_B2_LDS) {
-    VariantCall c;
-    c.P = P, c.grid = grid, c.st = st, c.trav = trav, c.stats = STATS, c.hits = HITS, c.small = small;
-    variant_launch(VOP_RENDER_FULL, c);
-    return;
-  }
-  const dim3 g(grid * (4 / kFullWPB) + 3 * P.split_k), b(64 * kFullWPB);
-  if (!STATS && small) hipLaunchKernelGGL((k_render_full<STATS, HITS, TRAV_B2_LDS, kFullWavesPerEuSmall>), g, b, 0, st, P);
-  else hipLaunchKernelGGL((k_render_full<STATS, HITS, TRAV_B2_LDS>), g, b, 0, st, P);
-}
-
 // The variants library defines the strong variant_launch / variants_linked (rt_variants.hip); in the
 // product library these weak defaults stand, and rt_render_async refuses a variant-only frame up front.
 __attribute__((weak)) bool variants_linked() { return false; }
@@ -1067,33 +1017,28 @@ static int check_device_scene(rt_scene* s) {
   return RT_OK;
 }
 
-extern "C" int rt_debug_timeline(rt_scene* s, int64_t capacity_waves, uint32_t* out8, int64_t* n_waves) {
+// the last frame's diagnostic records (8 words per wave) of kind `what`, which it kept if `have`
+static int read_wave_records(rt_scene* s, const char* who, const char* what, bool have, uint32_t* rt_scene::FrameSlot::*buf,
+                             int64_t waves, int64_t capacity_waves, uint32_t* out8, int64_t* n_waves) {
   int rc = check_device_scene(s);
   if (rc) return rc;
   const rt_scene::FrameSlot& f = s->slots[s->last_slot];
-  if (!(s->last_flags & RT_FRAME_TIMELINE) || !f.d_timeline) { set_error("rt_debug_timeline: last frame had no RT_FRAME_TIMELINE"); return RT_ERR_INVALID; }
-  if (n_waves) *n_waves = s->last_timeline_waves;
+  if (!have || !(f.*buf)) { set_error("%s: last frame had no %s", who, what); return RT_ERR_INVALID; }
+  if (n_waves) *n_waves = waves;
   if (!out8) return RT_OK;
-  if (capacity_waves < s->last_timeline_waves) { set_error("rt_debug_timeline: buffer too small"); return RT_ERR_INVALID; }
+  if (capacity_waves < waves) { set_error("%s: buffer too small", who); return RT_ERR_INVALID; }
   HIPCHECK(hipStreamSynchronize((hipStream_t)f.stream));
-  HIPCHECK(hipMemcpy(out8, f.d_timeline, (size_t)s->last_timeline_waves * 32, hipMemcpyDeviceToHost));
+  HIPCHECK(hipMemcpy(out8, f.*buf, (size_t)waves * 32, hipMemcpyDeviceToHost));
   return RT_OK;
 }
-
+extern "C" int rt_debug_timeline(rt_scene* s, int64_t capacity_waves, uint32_t* out8, int64_t* n_waves) {
+  return read_wave_records(s, "rt_debug_timeline", "RT_FRAME_TIMELINE", s && (s->last_flags & RT_FRAME_TIMELINE),
+                           &rt_scene::FrameSlot::d_timeline, s ? s->last_timeline_waves : 0, capacity_waves, out8, n_waves);
+}
 extern "C" int rt_debug_wave_stats(rt_scene* s, int64_t capacity_waves, uint32_t* out8, int64_t* n_waves) {
-  int rc = check_device_scene(s);
-  if (rc) return rc;
-  const rt_scene::FrameSlot& f = s->slots[s->last_slot];
-  if (!(s->last_flags & RT_FRAME_WAVE_STATS) || !(s->last_flags & RT_FRAME_STATS) || !f.d_wave_stats) {
-    set_error("rt_debug_wave_stats: last frame had no RT_FRAME_STATS | RT_FRAME_WAVE_STATS");
-    return RT_ERR_INVALID;
-  }
-  if (n_waves) *n_waves = s->last_wave_stats_waves;
-  if (!out8) return RT_OK;
-  if (capacity_waves < s->last_wave_stats_waves) { set_error("rt_debug_wave_stats: buffer too small"); return RT_ERR_INVALID; }
-  HIPCHECK(hipStreamSynchronize((hipStream_t)f.stream));
-  HIPCHECK(hipMemcpy(out8, f.d_wave_stats, (size_t)s->last_wave_stats_waves * 32, hipMemcpyDeviceToHost));
-  return RT_OK;
+  const int both = RT_FRAME_STATS | RT_FRAME_WAVE_STATS;
+  return read_wave_records(s, "rt_debug_wave_stats", "RT_FRAME_STATS | RT_FRAME_WAVE_STATS", s && (s->last_flags & both) == both,
+                           &rt_scene::FrameSlot::d_wave_stats, s ? s->last_wave_stats_waves : 0, capacity_waves, out8, n_waves);
 }
 
 extern "C" int rt_debug_counters(rt_scene* s, int64_t n, int64_t* out) {
@@ -1139,423 +1084,243 @@ extern "C" int rt_device_count(void) {
   return n;
 }
 
-// Super-tile width of a shard_count-way split (shard_tile_xy, rt_api.h rt_frame): 4x4 tiles (64x64
-// pixels) per super-tile when the frame is split, so that the waves an XCD runs together trace
-// neighbouring pixels (the rank's L2 working set stays compact): C4 over 8 / 4 GPUs +10% / +7% per GPU
-// against single tiles interleaved (profiles/ab/r02_super_tiles_ab.txt); an unsplit frame keeps its tile
-// order (super-tiles there: C3 +-1%, C4 -3%). A pure function of the shard count: the render,
-// rt_frame_shard_tiles, the pack on every rank and the unpack on rank 0 derive the same layout, whatever
-// the process environment or the kernel variant.
-static int frame_super_tile(int shard_count) { return shard_count > 1 ? kShardSuperTile : 1; }
-
-// one device's share of a frame (the whole frame on a single-device scene; a replica's shard otherwise)
-static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr) {
-  int rc = check_device_scene(s);
-  if (rc) return rc;
+static int check_frame_args(const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr) {
   if (!cam || !fr || fr->width <= 0 || fr->height <= 0 || n_lights < 0 || n_lights > RT_MAX_LIGHTS ||
       (n_lights && !lights)) {
     set_error("rt_render: invalid arguments");
     return RT_ERR_INVALID;
   }
-  if (fr->mode != RT_MODE_PRIMARY && fr->mode != RT_MODE_FULL && fr->mode != RT_MODE_BOX_COLORS) {
-    set_error("rt_render: bad mode %d", fr->mode);
-    return RT_ERR_INVALID;
-  }
+  if (fr->mode != RT_MODE_PRIMARY && fr->mode != RT_MODE_FULL && fr->mode != RT_MODE_BOX_COLORS) { set_error("rt_render: bad mode %d", fr->mode); return RT_ERR_INVALID; }
   if (fr->max_depth < 0 || fr->max_depth > RT_MAX_TRACE_DEPTH) {
     set_error("rt_render: max_depth %d outside 0..%d", fr->max_depth, RT_MAX_TRACE_DEPTH);
     return RT_ERR_INVALID;
   }
   const int sc = fr->shard_count > 0 ? fr->shard_count : 1;
-  const int si = fr->shard_index;
-  if (si < 0 || si >= sc) { set_error("rt_render: shard %d of %d", si, sc); return RT_ERR_INVALID; }
-  const size_t npix = (size_t)fr->width * fr->height;
-  const bool boxcol = fr->mode == RT_MODE_BOX_COLORS;
-  if (boxcol && (rc = ensure_face_boxcolor(s))) return rc;
-  // frames in flight: round-robin over the slots; a slot's stream orders its own frames, frames on
-  // different slots overlap (tail of one frame with the start of the next)
-  const int slot_id = s->next_slot;
-  rt_scene::FrameSlot& slot = s->slots[slot_id];
-  if ((rc = ensure_fb(slot, npix))) return rc;
-  FrameParams P;
-  fill_scene_params(s, P);
-  // camera (camera.hpp:115-118,155-173,263-266)
+  if (fr->shard_index < 0 || fr->shard_index >= sc) { set_error("rt_render: shard %d of %d", fr->shard_index, sc); return RT_ERR_INVALID; }
+  return RT_OK;
+}
+
+// calculateColor's order: point lights first, then directional lights (each in array order)
+static void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights) {
+  P.n_lights = n_lights;
+  int k = 0;
+  for (int pass = 0; pass < 2; pass++)
+    for (int l = 0; l < n_lights; l++) {
+      const int kind = lights[l].kind == RT_LIGHT_DIRECTIONAL ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT;
+      if (kind != (pass ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT)) continue;
+      memcpy(P.lights[k].p, lights[l].position, 12);
+      memcpy(P.lights[k].c, lights[l].color, 12);
+      P.lights[k].kind = kind;
+      k++;
+    }
+}
+
+// camera (camera.hpp:115-118,155-173,263-266) and lights of a frame; P.Minv is set (fill_scene_params)
+static void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights) {
   affinv(cam->view_matrix, P.vinv);
-  {
-    float L[9], Li[9];
-    linear_of(cam->view_matrix, L);
-    m3inv(L, Li);
-    const f3 e = m3v3(Li, f3{-cam->view_matrix[12], -cam->view_matrix[13], -cam->view_matrix[14]});
-    P.eye[0] = e.x; P.eye[1] = e.y; P.eye[2] = e.z;
-    const f3 eo = affv3(s->hs.Minv, e);
-    P.eye_obj[0] = eo.x; P.eye_obj[1] = eo.y; P.eye_obj[2] = eo.z;
-  }
+  float L[9], Li[9];
+  linear_of(cam->view_matrix, L);
+  m3inv(L, Li);
+  const f3 e = m3v3(Li, f3{-cam->view_matrix[12], -cam->view_matrix[13], -cam->view_matrix[14]});
+  P.eye[0] = e.x; P.eye[1] = e.y; P.eye[2] = e.z;
+  const f3 eo = affv3(P.Minv, e);
+  P.eye_obj[0] = eo.x; P.eye_obj[1] = eo.y; P.eye_obj[2] = eo.z;
   memcpy(P.vp, cam->viewport, 16);
   const float persp = (float)((double)1.0f / tan((double)(cam->fovy / 2.0f) * (M_PI / 180.0)));
   const float scale = (float)(1.0 / (double)persp);
   P.xscale = cam->aspect_ratio * scale;
   P.yscale = scale;
-  P.n_lights = n_lights;
-  {  // calculateColor's order: point lights first, then directional lights (each in array order)
-    int k = 0;
-    for (int pass = 0; pass < 2; pass++)
-      for (int l = 0; l < n_lights; l++) {
-        const int kind = lights[l].kind == RT_LIGHT_DIRECTIONAL ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT;
-        if (kind != (pass ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT)) continue;
-        memcpy(P.lights[k].p, lights[l].position, 12);
-        memcpy(P.lights[k].c, lights[l].color, 12);
-        P.lights[k].kind = kind;
-        k++;
-      }
-  }
-  P.W = fr->width;
-  P.H = fr->height;
-  P.tiles_x = (fr->width + 15) / 16;
-  P.tiles_y = (fr->height + 15) / 16;
-  const int ntiles = P.tiles_x * P.tiles_y;
-  P.shard_index = si;
-  P.shard_count = sc;
-  P.super_tile = frame_super_tile(sc);
-  P.n_tiles_shard = shard_tile_slots(P.tiles_x, P.tiles_y, P.super_tile, si, sc);
-  (void)ntiles;
-  P.mode = fr->mode;
-  P.flags = fr->flags;
-  P.rgb = slot.d_rgb;
-  P.face_out = slot.d_face;
-  P.t_out = slot.d_t;
-  P.stats = s->d_stats;
-  P.hits = slot.d_hits;
-  P.face_boxcolor = s->d_face_boxcolor;
-  hipStream_t st = (hipStream_t)slot.stream;
-  const bool stats = (fr->flags & RT_FRAME_STATS) != 0;
-  const bool hits = (fr->flags & RT_FRAME_WRITE_HITS) != 0;
-  if (stats) {
-    // the counters are shared: a counting frame waits for every frame in flight on the other slots
-    for (int k = 0; k < s->n_slots; k++)
-      if (k != slot_id && s->slots[k].last_done) HIPCHECK(hipStreamWaitEvent(st, (hipEvent_t)s->slots[k].last_done, 0));
-    HIPCHECK(hipMemsetAsync(s->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
-  }
-  const int grid = P.n_tiles_shard;
-  const int variant = kernel_variant();
-  if (variant & 2097152) P.sc.wide_copy_bytes = 0;  // PRIMARY octant packets on the binary tree (A/B)
-  // PRIMARY with two packets per wave (k_primary_dual): variant bit 1048576
-  const bool dual = (fr->mode == RT_MODE_PRIMARY || fr->mode == RT_MODE_BOX_COLORS) && !stats &&
-                    (fr->max_depth <= 1 || fr->mode == RT_MODE_BOX_COLORS) && !(variant & (1 | 2 | 4 | 32768 | 256 | 2048 | 65536)) &&
-                    (variant & 1048576);
-  const size_t units = (size_t)grid * (dual ? 2 : 4);  // one-wave blocks of the render kernel
-  // (RT_TIMELINE_SPLIT, diagnostics only: a timeline frame keeps the lone-frame split of its costliest
-  // waves; one record per block, so room for the 3 K extra blocks)
-  const bool timeline_split = (fr->flags & RT_FRAME_TIMELINE) && debug_env("RT_TIMELINE_SPLIT");
-  if (fr->flags & RT_FRAME_TIMELINE) {  // one record per one-wave block of the render kernel
-    const size_t waves = timeline_split ? 2 * units : units;
-    if (waves > slot.timeline_waves) {
-      HIPCHECK(hipStreamSynchronize(st));
-      if (slot.d_timeline) (void)hipFree(slot.d_timeline);
-      slot.d_timeline = nullptr;
-      slot.timeline_waves = 0;
-      HIPCHECK(hipMalloc((void**)&slot.d_timeline, waves * 32));
-      slot.timeline_waves = waves;
-    }
-    HIPCHECK(hipMemsetAsync(slot.d_timeline, 0, waves * 32, st));
-    P.timeline = slot.d_timeline;
-    s->last_timeline_waves = (int64_t)waves;
-  }
-  if (stats && (fr->flags & RT_FRAME_WAVE_STATS)) {  // per logical wave (tile * 4 + quarter)
-    // the generic traceRay kernel (k_render_depth: any recursion limit but the mode's own, or variant 65536)
-    // writes no per-wave records: refuse the frame instead of returning all-zero records
-    const int own_depth = fr->mode == RT_MODE_FULL ? 2 : 1;
-    if (!boxcol && ((fr->max_depth > 0 && fr->max_depth != own_depth) || (variant & 65536))) {
-      set_error("rt_render: RT_FRAME_WAVE_STATS needs the mode's own max_depth (the generic-depth kernel keeps no per-wave counts)");
-      return RT_ERR_UNSUPPORTED;
-    }
-    const size_t lw = (size_t)grid * 4;
-    if (lw > slot.wave_stats_waves) {
-      HIPCHECK(hipStreamSynchronize(st));
-      if (slot.d_wave_stats) (void)hipFree(slot.d_wave_stats);
-      slot.d_wave_stats = nullptr;
-      slot.wave_stats_waves = 0;
-      HIPCHECK(hipMalloc((void**)&slot.d_wave_stats, lw * 32));
-      slot.wave_stats_waves = lw;
-    }
-    HIPCHECK(hipMemsetAsync(slot.d_wave_stats, 0, lw * 32, st));
-    P.wave_stats = slot.d_wave_stats;
-    s->last_wave_stats_waves = (int64_t)lw;
-  }
-  if (fr->mode == RT_MODE_FULL && (variant & 16)) {
-    if (sc > 1) { set_error("rt_render: the FULL stage-pipeline variant renders whole frames only"); return RT_ERR_UNSUPPORTED; }
-    // sized by the 16x16-padded frame: every wave of the tile grid has a count slot
-    const size_t npad = (size_t)P.tiles_x * 16 * (size_t)P.tiles_y * 16;
-    if ((rc = ensure_full(slot, npad))) return rc;
-    bind_full(slot, P);
-  }
-  // a frame alone on the GPU: no other frame of this scene in flight (the dispatch order below and the
-  // longest-first order depend on it)
-  bool alone = true;
-  for (int k = 0; k < s->n_slots; k++)
-    if (k != slot_id && s->slots[k].last_done && hipEventQuery((hipEvent_t)s->slots[k].last_done) == hipErrorNotReady)
-      alone = false;
-  // block order: chunked XCD order -- block b runs on XCD b % 8, and the XCD's k-th block takes the k-th
-  // position of its runs of C consecutive blocks. Scenes whose records exceed the chip's 32 MiB of L2 take
-  // one contiguous band of the frame per XCD (C = units / 8), so that each XCD's 4 MiB L2 holds the part
-  // of the scene its band sees (L2 hit 0.90 -> 0.94 on C3): a frame alone on the GPU +4.3% on C3, +8.7%
-  // on C4. With frames in flight the XCDs' bands rotate frame by frame (xcd_rot), so that no XCD keeps
-  // the costliest band of every frame: +1.5% on C3 at 100 frames (fixed bands lost 1-3% there); all in
-  // profiles/ab/r05_xcd_bands_ab.txt. L2-resident scenes keep runs of C = 64 (bunny one frame alone with
-  // bands: PRIMARY -9%, FULL -6..-12% -- no locality to gain, and the bands differ in cost; runs of
-  // 32 .. 256 within noise, profiles/ab/r05_xcd_run_ab.txt; 64 against the plain order -4% trace time on
-  // C3 before the bands). Variant bits 512 / 1024 select runs of 4 / 16 blocks, 1536 the plain dispatch
-  // order, 4 one contiguous tile range per XCD (256-thread blocks)
-  {
-    const int sel = (variant >> 9) & 3;
-    const bool l2_resident = (s->hs.nodes.size() + s->hs.tris.size()) * 64 <= kFullSmallSceneBytes;
-    const int run = l2_resident ? 64 : std::max<int>(2, (int)(units / 8));
-    P.xcd_remap = (variant & 4) ? 1 : (sel == 0 ? run : sel == 1 ? 4 : sel == 2 ? 16 : 0);
-    const char* run_env = debug_env("RT_XCD_RUN");  // (A/B only: another run length of the chunked order)
-    if (run_env && atoi(run_env) >= 2) P.xcd_remap = atoi(run_env);
-    if (!alone && !l2_resident && P.xcd_remap >= 2) P.xcd_rot = (int32_t)(s->band_rot++ & 7u);
-  }
-  const int trav = pick_trav(P, variant);
-  {
-    const bool prim_mode = fr->mode == RT_MODE_PRIMARY || boxcol;
-    const bool need = trav != TRAV_B2_LDS || dual || (fr->mode == RT_MODE_FULL && (variant & 16)) ||
-                      (prim_mode && !stats && (variant & (256 | 2048)));
-    if (need && !variants_linked()) {
-      set_error("rt_render: kernel variant %d is an A/B build option, not in this library (make variants)", variant);
-      return RT_ERR_UNSUPPORTED;
-    }
-  }
-  // longest-first dispatch (k_order_lpt) for the one-wave render kernels of the default build: this
-  // slot's previous frame of the same shape left its per-wave costs and the order computed from them
-  // box-colour frames return before any reflection: one depth, the PRIMARY kernels' dispatch
-  const bool prim = fr->mode == RT_MODE_PRIMARY || boxcol;
-  const int mode_depth0 = fr->mode == RT_MODE_FULL ? 2 : 1;
-  const int depth0 = (fr->max_depth > 0 && !boxcol) ? fr->max_depth : mode_depth0;
-  const bool one_wave_kernel = !stats && trav == TRAV_B2_LDS &&
-                               ((prim && depth0 == 1 && !(variant & (32768 | 256 | 2048 | 65536))) ||
-                                (fr->mode == RT_MODE_FULL && depth0 == 2 && !(variant & (16 | 65536))) ||
-                                (!boxcol && (depth0 != mode_depth0 || (variant & 65536))));
-  // Only for a frame that has the GPU to itself (no other frame of this scene in flight): then the
-  // tail of the frame would leave the GPU idle and longest-first fills it (one frame at a time: C3
-  // +18%, C5 +28%); with frames in flight the next frame fills the tail and the default order's tile
-  // locality is worth more (LPT measured -3..-7% there). Variant 524288 forces it, 131072 disables it.
-  // (variant 524288, A/B only: also with frames in flight -- then the map is shared by frames that overlap,
-  // a race on the order's values only: any order is a permutation)
-  const bool lpt = one_wave_kernel && !(variant & 131072) && P.xcd_remap >= 2 && grid > 0 && (alone || (variant & 524288));
-  bool lpt_sort = false;
-  int lpt_dilate = 0;
-  rt_scene::LptMap& lm = s->lpt;
-  if (lpt) {
-    const size_t waves = units;
-    if (waves > lm.waves) {
-      for (int k = 0; k < s->n_slots; k++) HIPCHECK(hipStreamSynchronize((hipStream_t)s->slots[k].stream));
-      if (lm.d_cost) (void)hipFree(lm.d_cost);
-      if (lm.d_cost_dil) (void)hipFree(lm.d_cost_dil);
-      if (lm.d_order) (void)hipFree(lm.d_order);
-      lm.d_cost = lm.d_cost_dil = lm.d_order = nullptr;
-      lm.waves = 0;
-      lm.valid = false;
-      HIPCHECK(hipMalloc((void**)&lm.d_cost, waves * 4));
-      HIPCHECK(hipMalloc((void**)&lm.d_cost_dil, waves * 4));
-      HIPCHECK(hipMalloc((void**)&lm.d_order, waves * 4));
-      HIPCHECK(hipMemsetAsync(lm.d_cost, 0, waves * 4, st));  // (each sort clears what it read after this)
-      HIPCHECK(hipMemsetAsync(lm.d_cost_dil, 0, waves * 4, st));
-      lm.waves = waves;
-    }
+  fill_lights(P, lights, n_lights);
+}
 
-    const int64_t key[8] = {fr->width, fr->height, si, sc, fr->mode, depth0, P.xcd_remap, (int64_t)waves};
-    const bool same = lm.valid && memcmp(key, lm.key, sizeof key) == 0;
-    if (same) P.order = lm.d_order;
-    // The order is recomputed from this frame's costs after the frame when it is missing, has served
-    // kLptRefresh frames, or -- kLptMoved -- the camera has moved since the frame that recorded it (the
-    // reference's Flycamera moves every frame while a key is held, flyscene.cpp:116-127): a moving camera then
-    // dispatches every lone frame by the previous frame's costs. The sort costs a few microseconds on the frame's
-    // stream. (RT_LPT_REFRESH / RT_LPT_MOVED: A/B knobs, debug environment only.)
-    const char* refresh_env = debug_env("RT_LPT_REFRESH");
-    const char* moved_env = debug_env("RT_LPT_MOVED");
-    const int refresh = refresh_env ? std::max(1, atoi(refresh_env)) : kLptRefresh;
-    const bool key_moved = moved_env ? atoi(moved_env) != 0 : kLptMoved;
-    const bool moved = memcmp(cam->view_matrix, lm.view, sizeof lm.view) != 0;
-    // moving: this frame's camera differs from the previous lone frame's -> its costs are placed where each wave's
-    // content is expected in the next frame (the camera repeating its step, FrameParams::pred) and dilated before the
-    // sort (whole frames only: the wave grid of a shard is not contiguous). RT_LPT_DILATE / RT_LPT_PRED: A/B knobs
-    const bool moving = memcmp(cam->view_matrix, lm.prev_view, sizeof lm.prev_view) != 0;
-    float prev_view[16];
-    memcpy(prev_view, lm.prev_view, sizeof prev_view);
-    memcpy(lm.prev_view, cam->view_matrix, sizeof lm.prev_view);
-    // Measured under the reference's moving camera (profiles/ab/r06_moving_camera_ab.txt, one frame at a time):
-    // an L2-resident scene whose lone frames split their costliest waves (C5: the bunny's silhouette tiles) loses
-    // the split's gain with a map even one frame old (0.38 ms against 0.227 with an exact map) and regains most
-    // of it with a fresh, dilated map (0.31 ms), more with the costs moved to their predicted waves (0.26 ms,
-    // profiles/ab/r06_moving_prediction_ab.txt); the soup's per-wave costs decorrelate within a frame of motion
-    // (fresh or 8 frames old, dilated or not: 0.233-0.237 ms, no map 0.245; predicted: 0.226 ms, but the sort on
-    // every frame's path takes it back), so large scenes keep the 8-frame refresh and spend no sort per frame.
-    // (RT_LPT_MOVED forces either rule.)
-    const bool l2_small = (s->hs.nodes.size() + s->hs.tris.size()) * 64 <= kFullSmallSceneBytes;
-    const bool resort_on_motion = moved_env ? key_moved : (key_moved && l2_small);
-    // (a dilated map is replaced by the first frame after the camera stopped: dilated, the map spends the split on
-    // the costly waves' neighbours -- 0.30 ms instead of 0.22 on C5 at an exact pose)
-    lpt_sort = !same || ++lm.age >= refresh || (resort_on_motion && moved) || (lm.dilated_map && !moving);
-    lm.frames++;
-    if (lpt_sort) {
-      memcpy(lm.key, key, sizeof key);
-      memcpy(lm.view, cam->view_matrix, sizeof lm.view);
-      lm.valid = false;  // until this frame's k_order_lpt has been queued
-      P.cost = lm.d_cost;
-      lm.sorts++;
-      // RT_LPT_PRED (A/B knob): each wave's cost lands where its content is expected next frame (FrameParams::pred)
-      const char* pred_env = debug_env("RT_LPT_PRED");
-      const bool pred = pred_env ? atoi(pred_env) != 0 : kLptPred;
-      const char* dil_env = debug_env("RT_LPT_DILATE");  // (2 + 2 r)^2 <= 64 lanes
-      const int r = dil_env ? std::max(0, std::min(3, atoi(dil_env))) : (pred ? kLptDilatePred : kLptDilate);
-      const char* dilw_env = debug_env("RT_LPT_DILW");  // A/B knob: the ring's weight 1 - 2^-w (default 3/4)
-      const int dil_w = dilw_env ? std::max(1, std::min(8, atoi(dilw_env))) : 2;
-      const bool moving_map = moving && resort_on_motion && sc == 1 && !dual && (r > 0 || pred);
-      lpt_dilate = moving_map;
-      lm.dilated_map = moving_map;
-      if (moving_map) {
-        lm.dilated++;
-        P.cost_dil = lm.d_cost_dil;
-        P.dil_r = r;
-        P.dil_w = dil_w;
-        if (pred) {  // a pixel's view-space direction (nx xscale, ny yscale, -1) as (a px + b, c py + e, -1)
-          P.pred = 1;
-          P.pred_proj[0] = 2.0f * P.xscale / P.vp[2];
-          P.pred_proj[1] = -(2.0f * P.vp[0] / P.vp[2] + 1.0f) * P.xscale;
-          P.pred_proj[2] = -2.0f * P.yscale / P.vp[3];
-          P.pred_proj[3] = (1.0f + 2.0f * P.vp[1] / P.vp[3]) * P.yscale;
-          camera_step(prev_view, cam->view_matrix, P.pred_step);
-        }
-      }
-    }
+// a slot's diagnostic records (timeline, per-wave counts; 8 words per wave): room for `waves`, cleared on st
+static int ensure_wave_records(uint32_t*& ptr, size_t& capacity, size_t waves, hipStream_t st) {
+  if (waves > capacity) {
+    HIPCHECK(hipStreamSynchronize(st));
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr, capacity = 0;
+    HIPCHECK(hipMalloc((void**)&ptr, waves * 32));
+    capacity = waves;
   }
-  if (s->ev_used + 3 > s->ev_pool.size()) {  // (init_slots creates kEventFrames frames' worth up front)
-    if (s->ev_pool.size() >= 3 * 2048) { set_error("more than 2048 renders without rt_synchronize"); return RT_ERR_INVALID; }
-    for (int k = 0; k < 3; k++) {
-      hipEvent_t e;
-      HIPCHECK(hipEventCreate(&e));
-      s->ev_pool.push_back(e);
+  HIPCHECK(hipMemsetAsync(ptr, 0, waves * 32, st));
+  return RT_OK;
+}
+
+// Longest-first dispatch of a lone frame (plan.lpt): binds the order the scene's previous lone frame of this shape
+// left; `sort`: this frame records its costs and lpt_end sorts them after it, `dilated`: from a moving camera's map
+static int lpt_begin(rt_scene* s, const FramePlan& plan, const rt_camera* cam, hipStream_t st, FrameParams& P, bool& sort,
+                     bool& dilated) {
+  rt_scene::LptMap& lm = s->lpt;
+  const size_t waves = plan.units;
+  if (waves > lm.waves) {
+    for (int k = 0; k < s->n_slots; k++) HIPCHECK(hipStreamSynchronize((hipStream_t)s->slots[k].stream));
+    lm.waves = 0, lm.valid = false;
+    for (uint32_t** p : {&lm.d_cost, &lm.d_cost_dil, &lm.d_order}) {
+      if (*p) (void)hipFree(*p);
+      *p = nullptr;
+      HIPCHECK(hipMalloc((void**)p, waves * 4));
     }
+    HIPCHECK(hipMemsetAsync(lm.d_cost, 0, waves * 4, st));  // (each sort clears what it read after this)
+    HIPCHECK(hipMemsetAsync(lm.d_cost_dil, 0, waves * 4, st));
+    lm.waves = waves;
   }
-  // three events per frame: start | after the traversal kernel | after the frame
-  hipEvent_t ev_a = (hipEvent_t)s->ev_pool[s->ev_used], ev_m = (hipEvent_t)s->ev_pool[s->ev_used + 1],
-             ev_b = (hipEvent_t)s->ev_pool[s->ev_used + 2];
-  s->ev_used += 3;
-  HIPCHECK(hipEventRecord(ev_a, st));
-  const int mode_depth = fr->mode == RT_MODE_FULL ? 2 : 1;
-  const int depth = depth0;
-  P.max_depth = depth;
-  P.shadows = fr->mode == RT_MODE_FULL ? 1 : 0;
-  if (grid > 0 && !boxcol && (depth != mode_depth || (variant & 65536))) {
-    // any other recursion limit: the generic traceRay kernel (one 8x8 wave per block)
-    const dim3 g(grid * 4), b(64);
-    if (stats) { if (hits) hipLaunchKernelGGL((k_render_depth<true, true>), g, b, 0, st, P); else hipLaunchKernelGGL((k_render_depth<true, false>), g, b, 0, st, P); }
-    else { if (hits) hipLaunchKernelGGL((k_render_depth<false, true>), g, b, 0, st, P); else hipLaunchKernelGGL((k_render_depth<false, false>), g, b, 0, st, P); }
-    HIPCHECK(hipGetLastError());
-    HIPCHECK(hipEventRecord(ev_m, st));
-  } else if (grid > 0) {
-    if (dual && grid > 0) {
-      VariantCall vc;
-      vc.P = P, vc.units = units, vc.st = st, vc.hits = hits, vc.boxcol = boxcol;
+  const int64_t key[8] = {P.W, P.H, P.shard_index, P.shard_count, P.mode, plan.depth, plan.xcd_remap, (int64_t)waves};
+  const bool same = lm.valid && memcmp(key, lm.key, sizeof key) == 0;
+  if (same) P.order = lm.d_order;
+  // The order is recomputed from this frame's costs after the frame when it is missing, has served
+  // kLptRefresh frames, or -- kLptMoved -- the camera has moved since the frame that recorded it (the
+  // reference's Flycamera moves every frame while a key is held, flyscene.cpp:116-127): a moving camera then
+  // dispatches every lone frame by the previous frame's costs. The sort costs a few microseconds on the frame's
+  // stream. (RT_LPT_REFRESH / RT_LPT_MOVED: A/B knobs, debug environment only.)
+  const int refresh = knob_int("RT_LPT_REFRESH", kLptRefresh, 1, INT_MAX);
+  const int moved_knob = knob_int("RT_LPT_MOVED", kKnobUnset, INT_MIN, INT_MAX);
+  const bool moved = memcmp(cam->view_matrix, lm.view, sizeof lm.view) != 0;
+  // moving: this frame's camera differs from the previous lone frame's -> its costs are placed where each wave's
+  // content is expected in the next frame (the camera repeating its step, FrameParams::pred) and dilated before the
+  // sort (whole frames only: the wave grid of a shard is not contiguous). RT_LPT_DILATE / RT_LPT_PRED: A/B knobs
+  const bool moving = memcmp(cam->view_matrix, lm.prev_view, sizeof lm.prev_view) != 0;
+  float prev_view[16];
+  memcpy(prev_view, lm.prev_view, sizeof prev_view);
+  memcpy(lm.prev_view, cam->view_matrix, sizeof lm.prev_view);
+  // Measured under the reference's moving camera (profiles/ab/r06_moving_camera_ab.txt, one frame at a time):
+  // an L2-resident scene whose lone frames split their costliest waves (C5: the bunny's silhouette tiles) loses
+  // the split's gain with a map even one frame old (0.38 ms against 0.227 with an exact map) and regains most
+  // of it with a fresh, dilated map (0.31 ms), more with the costs moved to their predicted waves (0.26 ms,
+  // profiles/ab/r06_moving_prediction_ab.txt); the soup's per-wave costs decorrelate within a frame of motion
+  // (fresh or 8 frames old, dilated or not: 0.233-0.237 ms, no map 0.245; predicted: 0.226 ms, but the sort on
+  // every frame's path takes it back), so large scenes keep the 8-frame refresh and spend no sort per frame.
+  // (RT_LPT_MOVED forces either rule.)
+  const bool resort_on_motion = moved_knob != kKnobUnset ? moved_knob != 0 : (kLptMoved && plan.l2_resident);
+  // (a dilated map is replaced by the first frame after the camera stopped: dilated, the map spends the split on
+  // the costly waves' neighbours -- 0.30 ms instead of 0.22 on C5 at an exact pose)
+  sort = !same || ++lm.age >= refresh || (resort_on_motion && moved) || (lm.dilated_map && !moving);
+  lm.frames++;
+  if (!sort) return RT_OK;
+  memcpy(lm.key, key, sizeof key);
+  memcpy(lm.view, cam->view_matrix, sizeof lm.view);
+  lm.valid = false;  // until this frame's k_order_lpt has been queued
+  P.cost = lm.d_cost;
+  lm.sorts++;
+  // RT_LPT_PRED (A/B knob): each wave's cost lands where its content is expected next frame (FrameParams::pred)
+  const bool pred = knob_int("RT_LPT_PRED", kLptPred, INT_MIN, INT_MAX) != 0;
+  const int r = knob_int("RT_LPT_DILATE", pred ? kLptDilatePred : kLptDilate, 0, 3);  // (2 + 2 r)^2 <= 64 lanes
+  dilated = moving && resort_on_motion && P.shard_count == 1 && plan.kernel != FK_PRIMARY_DUAL && (r > 0 || pred);
+  lm.dilated_map = dilated;
+  if (!dilated) return RT_OK;
+  lm.dilated++;
+  P.cost_dil = lm.d_cost_dil;
+  P.dil_r = r;
+  if (pred) {  // a pixel's view-space direction (nx xscale, ny yscale, -1) as (a px + b, c py + e, -1)
+    P.pred = 1;
+    P.pred_proj[0] = 2.0f * P.xscale / P.vp[2];
+    P.pred_proj[1] = -(2.0f * P.vp[0] / P.vp[2] + 1.0f) * P.xscale;
+    P.pred_proj[2] = -2.0f * P.yscale / P.vp[3];
+    P.pred_proj[3] = (1.0f + 2.0f * P.vp[1] / P.vp[3]) * P.yscale;
+    camera_step(prev_view, cam->view_matrix, P.pred_step);
+  }
+  return RT_OK;
+}
+
+// the sort for the scene's next lone frame of this shape, on this frame's stream before its done event: the next
+// lone frame is queued only once every other slot's done event has passed (`alone`), so it finds the order
+// complete whichever slot it takes
+static int lpt_end(rt_scene* s, const FramePlan& plan, hipStream_t st, bool dilated) {
+  rt_scene::LptMap& lm = s->lpt;
+  hipLaunchKernelGGL(k_order_lpt, dim3(8), dim3(kLptThreads), 0, st, dilated ? lm.d_cost_dil : lm.d_cost,
+                     dilated ? lm.d_cost : (uint32_t*)nullptr, lm.d_order, (int)plan.units, plan.xcd_remap,
+                     plan.lpt_coarse ? 1 : 0);
+  HIPCHECK(hipGetLastError());
+  lm.valid = true, lm.age = 0;
+  return RT_OK;
+}
+
+// the frame's render launches; ev_m is recorded after the traversal kernel
+static_assert(kTraceWPB == 1 && kFullWPB == 1, "the wave split (FrameParams::split_k) is per one-wave block");
+static int launch_frame(const FramePlan& plan, rt_scene* s, rt_scene::FrameSlot& slot, FrameParams& P, hipStream_t st,
+                        hipEvent_t ev_m) {
+  const int grid = plan.grid;
+  const bool stats = (P.flags & RT_FRAME_STATS) != 0, hits = (P.flags & RT_FRAME_WRITE_HITS) != 0;
+  const bool boxcol = P.mode == RT_MODE_BOX_COLORS;
+  // A lone frame of a small (L2-resident) scene, dispatched longest-first, splits its costliest waves
+  // into 16-lane sub-waves (FrameParams::split_k; RT_SPLIT_K / RT_SPLIT_KP waves, rounded down to a multiple
+  // of 8 and at most a quarter of the frame's waves), in k_render_full and in k_primary_fused: such a frame's
+  // span is its slowest waves' (C5 one frame alone: 2.2 resident waves per SIMD on average), and a 16-ray packet
+  // of their incoherent secondary rays finishes sooner. A large scene's FULL frame is not tail bound (5.7
+  // resident waves per SIMD on the soup) and the extra waves only cost (-6%), so it keeps whole waves. Results do
+  // not depend on the grouping (exact per-lane culling, (t, rank) argmin).
+  // (sub-waves take the max into the cost map, which the previous sort left at zero)
+  P.split_k = P.order ? plan.split_ceiling : 0;
+  VariantCall vc;
+  switch (plan.kernel) {
+    case FK_NONE: break;
+    case FK_GENERIC_DEPTH:  // one 8x8 wave per block
+      with_bools([&](auto S, auto H) { hipLaunchKernelGGL((k_render_depth<S.value, H.value>), dim3(grid * 4), dim3(64), 0, st, P); },
+                 stats, hits);
+      break;
+    case FK_PRIMARY_DUAL:
+      vc.P = P, vc.units = plan.units, vc.st = st, vc.hits = hits, vc.boxcol = boxcol;
       variant_launch(VOP_PRIMARY_DUAL, vc);
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(ev_m, st));
-    } else if (prim && !stats && !(variant & (32768 | 256 | 2048)) && trav == TRAV_B2_LDS) {
-      // lone frames of small scenes: the costliest waves as 16-lane sub-waves, as k_render_full does
-      // (RT_SPLIT_KP waves)
-      const char* split_p_env = debug_env("RT_SPLIT_KP");
-      const int split_p = split_p_env ? atoi(split_p_env) : kSplitKPrimary;
-      // (RT_SPLIT_KP_ANY, A/B only: split lone frames of any scene size)
-      const bool small_p = (s->hs.nodes.size() + s->hs.tris.size()) * 64 <= kFullSmallSceneBytes || debug_env("RT_SPLIT_KP_ANY");
-      P.split_k = (P.order && small_p && (!P.timeline || timeline_split) && kTraceWPB == 1)
-                      ? std::max(0, std::min<int>(split_p, (int)(units / 4))) & ~7 : 0;
-      // (sub-waves take the max into the cost map, which the previous sort left at zero)
+      break;
+    case FK_PRIMARY_FUSED: {
       const dim3 g(grid * (4 / kTraceWPB) + 3 * P.split_k), b(64 * kTraceWPB);
       // RT_LDS_PAD (diagnostics): extra dynamic LDS per block, to cap the resident waves per CU in
       // occupancy experiments (160 KiB / (pad + 1 KiB) blocks per CU)
-      const char* lds_pad_env = debug_env("RT_LDS_PAD");
-      const unsigned lds_pad = lds_pad_env ? (unsigned)atoi(lds_pad_env) : 0u;
-      if (boxcol) {
-        if (hits) hipLaunchKernelGGL((k_primary_fused<true, true>), g, b, lds_pad, st, P);
-        else hipLaunchKernelGGL((k_primary_fused<false, true>), g, b, lds_pad, st, P);
+      const unsigned lds_pad = (unsigned)knob_int("RT_LDS_PAD", 0, INT_MIN, INT_MAX);
+      with_bools([&](auto H, auto B) { hipLaunchKernelGGL((k_primary_fused<H.value, B.value>), g, b, lds_pad, st, P); }, hits,
+                 boxcol);
+      break;
+    }
+    case FK_PRIMARY_TRACE_SHADE:
+      if (plan.trav != TRAV_B2_LDS) {
+        vc.P = P, vc.grid = grid, vc.st = st, vc.trav = plan.trav, vc.stats = stats;
+        variant_launch(VOP_TRACE_PRIMARY, vc);
       } else {
-        if (hits) hipLaunchKernelGGL(k_primary_fused<true>, g, b, lds_pad, st, P);
-        else hipLaunchKernelGGL(k_primary_fused<false>, g, b, lds_pad, st, P);
+        with_bools([&](auto S) { hipLaunchKernelGGL((k_trace_primary<S.value, TRAV_B2_LDS>), dim3(grid * (4 / kTraceWPB)), dim3(64 * kTraceWPB), 0, st, P); },
+                   stats);
       }
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(ev_m, st));
-    } else if (prim) {
-      if (stats) launch_trace<true>(P, grid, st, trav);
-      else if ((variant & 256) && trav == TRAV_B2_LDS) {
-        VariantCall vc;
-        vc.P = P, vc.grid = grid, vc.st = st;
-        variant_launch(VOP_PRIMARY_X2, vc);
-      } else if ((variant & 2048) && trav == TRAV_B2_LDS && !P.wcount0) {
-        if (!slot.d_queue) HIPCHECK(hipMalloc((void**)&slot.d_queue, 8 * sizeof(uint32_t)));
-        HIPCHECK(hipMemsetAsync(slot.d_queue, 0, 8 * sizeof(uint32_t), st));
-        VariantCall vc;
-        vc.P = P, vc.grid = grid, vc.st = st, vc.variant = variant, vc.device = s->device, vc.queue = slot.d_queue;
-        variant_launch(VOP_PRIMARY_PERSISTENT, vc);
-      }
-      else launch_trace<false>(P, grid, st, trav);
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(ev_m, st));
-      if (boxcol) {
-        if (hits) hipLaunchKernelGGL((k_shade_primary<true, true>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_shade_primary<false, true>), dim3(grid), dim3(256), 0, st, P);
+      break;
+    case FK_PRIMARY_TWO_RAYS:
+      vc.P = P, vc.grid = grid, vc.st = st;
+      variant_launch(VOP_PRIMARY_X2, vc);
+      break;
+    case FK_PRIMARY_PERSISTENT:
+      if (!slot.d_queue) HIPCHECK(hipMalloc((void**)&slot.d_queue, 8 * sizeof(uint32_t)));
+      HIPCHECK(hipMemsetAsync(slot.d_queue, 0, 8 * sizeof(uint32_t), st));
+      vc.P = P, vc.grid = grid, vc.st = st, vc.variant = plan.variant, vc.device = s->device, vc.queue = slot.d_queue;
+      variant_launch(VOP_PRIMARY_PERSISTENT, vc);
+      break;
+    case FK_FULL_MEGAKERNEL:  // occupancy by scene size (plan.full_small_build; a counting run keeps the 8-wave build)
+      if (plan.trav != TRAV_B2_LDS) {
+        vc.P = P, vc.grid = grid, vc.st = st, vc.trav = plan.trav, vc.stats = stats, vc.hits = hits, vc.small = plan.full_small_build;
+        variant_launch(VOP_RENDER_FULL, vc);
       } else {
-        if (hits) hipLaunchKernelGGL((k_shade_primary<true, false>), dim3(grid), dim3(256), 0, st, P);
-        else hipLaunchKernelGGL((k_shade_primary<false, false>), dim3(grid), dim3(256), 0, st, P);
+        const dim3 g(grid * (4 / kFullWPB) + 3 * P.split_k), b(64 * kFullWPB);
+        with_bools([&](auto S, auto H, auto SMALL) {
+          hipLaunchKernelGGL((k_render_full<S.value, H.value, TRAV_B2_LDS, SMALL.value ? kFullWavesPerEuSmall : kFullWavesPerEu>), g, b, 0, st, P);
+        }, stats, hits, !stats && plan.full_small_build);
       }
-    } else if (!(variant & 16)) {  // FULL as one kernel (default); 16 = the stage pipeline
-      // occupancy by scene size (k_render_full); variant bits 8192 / 16384 force the 8-wave / small build
-      const size_t rec_bytes = (s->hs.nodes.size() + s->hs.tris.size()) * 64;
-      const bool small = (variant & 16384) || (!(variant & 8192) && rec_bytes <= kFullSmallSceneBytes);
-      // a lone frame of a small (L2-resident) scene, dispatched longest-first, splits its costliest waves
-      // into 16-lane sub-waves (FrameParams::split_k; RT_SPLIT_K waves, rounded down to a multiple of 8
-      // and at most a quarter of the frame's waves): such a frame's span is its slowest waves' (C5 one
-      // frame alone: 2.2 resident waves per SIMD on average), and a 16-ray packet of their incoherent
-      // secondary rays finishes sooner. A large scene's FULL frame is not tail bound (5.7 resident waves
-      // per SIMD on the soup) and the extra waves only cost (-6%), so it keeps whole waves. Results do not
-      // depend on the grouping (exact per-lane culling, (t, rank) argmin).
-      const char* split_k_env = debug_env("RT_SPLIT_K");
-      const int split_env = split_k_env ? atoi(split_k_env) : kSplitK;
-      if (P.order && small && (!P.timeline || timeline_split) && !stats && kFullWPB == 1 && trav == TRAV_B2_LDS)
-        P.split_k = std::max(0, std::min<int>(split_env, (int)(units / 4))) & ~7;
-      else
-        P.split_k = 0;
-      // (sub-waves take the max into the cost map, which the previous sort left at zero)
-      if (stats) { if (hits) launch_full<true, true>(P, grid, st, trav, small); else launch_full<true, false>(P, grid, st, trav, small); }
-      else { if (hits) launch_full<false, true>(P, grid, st, trav, small); else launch_full<false, false>(P, grid, st, trav, small); }
-      HIPCHECK(hipEventRecord(ev_m, st));
-    } else {
-      VariantCall vc;
-      vc.P = P, vc.grid = grid, vc.st = st, vc.trav = trav, vc.variant = variant, vc.stats = stats, vc.hits = hits,
+      break;
+    case FK_FULL_PIPELINE:  // records ev_m itself, before its last stage
+      vc.P = P, vc.grid = grid, vc.st = st, vc.trav = plan.trav, vc.variant = plan.variant, vc.stats = stats, vc.hits = hits,
       vc.ev_m = ev_m;
       variant_launch(VOP_FULL_PIPELINE, vc);
-    }
-    HIPCHECK(hipGetLastError());
-  } else {
-    HIPCHECK(hipEventRecord(ev_m, st));
+      break;
   }
-  // the sort for the scene's next lone frame of this shape, on this frame's stream before its done event: the next
-  // lone frame is queued only once every other slot's done event has passed (`alone`), so it finds the order
-  // complete whichever slot it takes
-  if (lpt_sort) {
-    uint32_t* in = lpt_dilate ? lm.d_cost_dil : lm.d_cost;
-    hipLaunchKernelGGL(k_order_lpt, dim3(8), dim3(kLptThreads), 0, st, in, lpt_dilate ? lm.d_cost : (uint32_t*)nullptr,
-                       lm.d_order, (int)units, P.xcd_remap, (variant & 262144) ? 1 : 0);
+  HIPCHECK(hipGetLastError());
+  if (plan.kernel != FK_FULL_PIPELINE) HIPCHECK(hipEventRecord(ev_m, st));
+  if (plan.kernel == FK_PRIMARY_TRACE_SHADE || plan.kernel == FK_PRIMARY_TWO_RAYS || plan.kernel == FK_PRIMARY_PERSISTENT) {
+    with_bools([&](auto H, auto B) { hipLaunchKernelGGL((k_shade_primary<H.value, B.value>), dim3(grid), dim3(256), 0, st, P); },
+               hits, boxcol);
     HIPCHECK(hipGetLastError());
-    lm.valid = true;
-    lm.age = 0;
   }
-  HIPCHECK(hipEventRecord(ev_b, st));
-  slot.last_done = ev_b;
-  s->last_slot = slot_id;
-  s->next_slot = (slot_id + 1) % s->n_slots;
-  s->last_W = fr->width;
-  s->last_H = fr->height;
-  s->last_shard_index = si;
-  s->last_shard_count = sc;
-  s->last_flags = fr->flags;
+  return RT_OK;
+}
+
+// what rt_synchronize, the downloads and the debug readers need to know about the frame just queued
+static void note_frame(rt_scene* s, int slot_id, const rt_frame* fr, const FrameParams& P) {
+  const int si = P.shard_index, sc = P.shard_count;
+  s->last_slot = slot_id, s->next_slot = (slot_id + 1) % s->n_slots;
+  s->last_W = fr->width, s->last_H = fr->height, s->last_shard_index = si, s->last_shard_count = sc, s->last_flags = fr->flags;
   // primary rays of this shard: pixels inside the frame of the shard's tiles (a walk over the shard's tiles,
   // done once per frame shape: it is host time on every frame's enqueue path otherwise)
   const int64_t rkey[4] = {fr->width, fr->height, si, sc};
@@ -1572,6 +1337,101 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
   }
   s->last_rays = s->rays_of_key;
   s->pending = true;
+}
+
+// one device's share of a frame (the whole frame on a single-device scene; a replica's shard otherwise)
+static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr) {
+  int rc = check_device_scene(s);
+  if (rc || (rc = check_frame_args(cam, lights, n_lights, fr))) return rc;
+  const int sc = fr->shard_count > 0 ? fr->shard_count : 1, si = fr->shard_index;
+  if (fr->mode == RT_MODE_BOX_COLORS && (rc = ensure_face_boxcolor(s))) return rc;
+  // frames in flight: round-robin over the slots; a slot's stream orders its own frames, frames on
+  // different slots overlap (tail of one frame with the start of the next)
+  const int slot_id = s->next_slot;
+  rt_scene::FrameSlot& slot = s->slots[slot_id];
+  if ((rc = ensure_fb(slot, (size_t)fr->width * fr->height))) return rc;
+  hipStream_t st = (hipStream_t)slot.stream;
+  FrameParams P;
+  fill_scene_params(s, P);
+  fill_camera_lights(P, cam, lights, n_lights);
+  P.W = fr->width, P.H = fr->height, P.tiles_x = (fr->width + 15) / 16, P.tiles_y = (fr->height + 15) / 16;
+  P.shard_index = si, P.shard_count = sc, P.super_tile = frame_super_tile(sc);
+  P.mode = fr->mode, P.flags = fr->flags, P.shadows = fr->mode == RT_MODE_FULL ? 1 : 0;
+  P.rgb = slot.d_rgb, P.face_out = slot.d_face, P.t_out = slot.d_t, P.hits = slot.d_hits;
+  P.stats = s->d_stats, P.face_boxcolor = s->d_face_boxcolor;
+  if (fr->flags & RT_FRAME_STATS) {
+    // the counters are shared: a counting frame waits for every frame in flight on the other slots
+    for (int k = 0; k < s->n_slots; k++)
+      if (k != slot_id && s->slots[k].last_done) HIPCHECK(hipStreamWaitEvent(st, (hipEvent_t)s->slots[k].last_done, 0));
+    HIPCHECK(hipMemsetAsync(s->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
+  }
+  FrameInputs in;
+  in.mode = fr->mode, in.max_depth = fr->max_depth, in.flags = fr->flags;
+  in.tiles_x = P.tiles_x, in.tiles_y = P.tiles_y, in.shard_index = si, in.shard_count = sc;
+  in.variant = kernel_variant(), in.has_wide4 = P.sc.n_nodes4 > 0;
+  in.record_bytes = (uint64_t)(s->hs.nodes.size() + s->hs.tris.size()) * 64;
+  // a frame alone on the GPU: no other frame of this scene in flight (the block order and the longest-first
+  // order depend on it)
+  for (int k = 0; k < s->n_slots; k++)
+    if (k != slot_id && s->slots[k].last_done && hipEventQuery((hipEvent_t)s->slots[k].last_done) == hipErrorNotReady)
+      in.alone = false;
+  in.split_k = knob_int("RT_SPLIT_K", kSplitK, 0, INT_MAX);
+  in.split_kp = knob_int("RT_SPLIT_KP", kSplitKPrimary, 0, INT_MAX);
+  // (RT_TIMELINE_SPLIT, diagnostics only: a timeline frame keeps the lone-frame split of its costliest
+  // waves; one record per block, so room for the 3 K extra blocks)
+  in.timeline_split = knob_int("RT_TIMELINE_SPLIT", kKnobUnset, INT_MIN, INT_MAX) != kKnobUnset;
+  const FramePlan plan = plan_frame(in);
+  P.n_tiles_shard = plan.grid;
+  P.max_depth = plan.depth;
+  if (plan.primary_binary_tree) P.sc.wide_copy_bytes = 0;
+  if (fr->flags & RT_FRAME_TIMELINE) {  // one record per one-wave block of the render kernel
+    const size_t waves = in.timeline_split ? 2 * plan.units : plan.units;
+    if ((rc = ensure_wave_records(slot.d_timeline, slot.timeline_waves, waves, st))) return rc;
+    P.timeline = slot.d_timeline;
+    s->last_timeline_waves = (int64_t)waves;
+  }
+  if ((fr->flags & RT_FRAME_STATS) && (fr->flags & RT_FRAME_WAVE_STATS)) {  // per logical wave (tile * 4 + quarter)
+    // the generic traceRay kernel writes no per-wave records: refuse the frame instead of returning all-zero records
+    if (!plan.writes_wave_stats) {
+      set_error("rt_render: RT_FRAME_WAVE_STATS needs the mode's own max_depth (the generic-depth kernel keeps no per-wave counts)");
+      return RT_ERR_UNSUPPORTED;
+    }
+    const size_t lw = (size_t)plan.grid * 4;
+    if ((rc = ensure_wave_records(slot.d_wave_stats, slot.wave_stats_waves, lw, st))) return rc;
+    P.wave_stats = slot.d_wave_stats;
+    s->last_wave_stats_waves = (int64_t)lw;
+  }
+  if (plan.pipeline_buffers) {
+    if (sc > 1) { set_error("rt_render: the FULL stage-pipeline variant renders whole frames only"); return RT_ERR_UNSUPPORTED; }
+    // sized by the 16x16-padded frame: every wave of the tile grid has a count slot
+    if ((rc = ensure_full(slot, (size_t)P.tiles_x * 16 * (size_t)P.tiles_y * 16))) return rc;
+    bind_full(slot, P);
+  }
+  P.xcd_remap = plan.xcd_remap;
+  if (plan.rotate_bands) P.xcd_rot = (int32_t)(s->band_rot++ & 7u);  // frames in flight: a large scene's XCD bands rotate
+  if (plan.needs_variants && !variants_linked()) {
+    set_error("rt_render: kernel variant %d is an A/B build option, not in this library (make variants)", in.variant);
+    return RT_ERR_UNSUPPORTED;
+  }
+  bool lpt_sort = false, lpt_dilated = false;
+  if (plan.lpt && (rc = lpt_begin(s, plan, cam, st, P, lpt_sort, lpt_dilated))) return rc;
+  if (s->ev_used + 3 > s->ev_pool.size()) {  // (init_slots creates kEventFrames frames' worth up front)
+    if (s->ev_pool.size() >= 3 * 2048) { set_error("more than 2048 renders without rt_synchronize"); return RT_ERR_INVALID; }
+    for (int k = 0; k < 3; k++) {
+      hipEvent_t e;
+      HIPCHECK(hipEventCreate(&e));
+      s->ev_pool.push_back(e);
+    }
+  }
+  // three events per frame: start | after the traversal kernel | after the frame
+  hipEvent_t* ev = (hipEvent_t*)&s->ev_pool[s->ev_used];
+  s->ev_used += 3;
+  HIPCHECK(hipEventRecord(ev[0], st));
+  if ((rc = launch_frame(plan, s, slot, P, st, ev[1]))) return rc;
+  if (lpt_sort && (rc = lpt_end(s, plan, st, lpt_dilated))) return rc;
+  HIPCHECK(hipEventRecord(ev[2], st));
+  slot.last_done = ev[2];
+  note_frame(s, slot_id, fr, P);
   return RT_OK;
 }
 
@@ -2314,19 +2174,7 @@ static int trace_rays(rt_scene* s, int query, int32_t n, const float* o, const f
   if (n == 0) return RT_OK;
   FrameParams P;
   fill_scene_params(s, P);
-  if (query == Q_COLOR) {  // calculateColor's order: point lights, then directional lights
-    int k = 0;
-    for (int pass = 0; pass < 2; pass++)
-      for (int l = 0; l < n_lights; l++) {
-        const int kind = lights[l].kind == RT_LIGHT_DIRECTIONAL ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT;
-        if (kind != (pass ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT)) continue;
-        memcpy(P.lights[k].p, lights[l].position, 12);
-        memcpy(P.lights[k].c, lights[l].color, 12);
-        P.lights[k].kind = kind;
-        k++;
-      }
-    P.n_lights = n_lights;
-  }
+  if (query == Q_COLOR) fill_lights(P, lights, n_lights);
   const size_t n3 = (size_t)n * 12;
   hipStream_t st = (hipStream_t)s->stream;
   std::vector<void*> bufs;
@@ -2360,7 +2208,7 @@ static int trace_rays(rt_scene* s, int query, int32_t n, const float* o, const f
     if (query == Q_COLOR && !(R.rgb = (float*)dalloc(n3))) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
   }
   const int grid = (n + 255) / 256;
-  const bool w4 = pick_trav(P, kernel_variant()) == TRAV_W4;
+  const bool w4 = pick_trav(kernel_variant(), P.sc.n_nodes4 > 0) == TRAV_W4;
   if (w4 && !variants_linked()) {
     set_error("trace: kernel variant %d is an A/B build option, not in this library (make variants)", kernel_variant());
     return RT_ERR_UNSUPPORTED;
@@ -2372,8 +2220,7 @@ static int trace_rays(rt_scene* s, int query, int32_t n, const float* o, const f
   } else if (query == Q_COLOR) {
     hipLaunchKernelGGL((k_rays_color<TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R);
   } else {
-    if (query == Q_SHADOW) hipLaunchKernelGGL((k_rays<true, TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R);
-    else hipLaunchKernelGGL((k_rays<false, TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R);
+    with_bools([&](auto ANY) { hipLaunchKernelGGL((k_rays<ANY.value, TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R); }, query == Q_SHADOW);
   }
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(st));

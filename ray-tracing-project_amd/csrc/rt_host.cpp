@@ -25,6 +25,7 @@
 #include <thread>
 #include <vector>
 
+#include "rt_dispatch.h"
 #include "rt_scene.h"
 
 using rt::f3;
@@ -34,6 +35,10 @@ static thread_local std::string g_err;
 static std::atomic<bool> g_debug_env{false};
 void set_debug_env(bool on) { g_debug_env.store(on); }
 const char* debug_env(const char* name) { return g_debug_env.load(std::memory_order_relaxed) ? getenv(name) : nullptr; }
+int knob_int(const char* name, int def, int lo, int hi) {
+  const char* e = debug_env(name);
+  return e ? std::max(lo, std::min(hi, atoi(e))) : def;
+}
 
 void set_error(const char* fmt, ...) {
   char buf[1024];
@@ -2587,6 +2592,26 @@ extern "C" int rt_debug_record_layout(int64_t n_nodes, int64_t n_tris, int64_t n
   uint64_t wb = 0;
   out[0] = (int64_t)rt::record_layout((uint64_t)n_nodes, (uint64_t)n_tris, (uint64_t)n_wide, &wb);
   out[1] = (int64_t)wb;
+  return RT_OK;
+}
+
+extern "C" int rt_debug_frame_plan(const int64_t in[], int32_t n_in, int32_t out[], int32_t n_out) {
+  if (!in || !out || n_in != 11 || n_out != 14 || in[3] <= 0 || in[4] <= 0 || in[3] > 65536 || in[4] > 65536 || in[6] < 1 ||
+      in[5] < 0 || in[5] >= in[6] || in[8] < 0) {
+    rt::set_error("rt_debug_frame_plan: bad argument");
+    return RT_ERR_INVALID;
+  }
+  rt::FrameInputs fi;
+  fi.mode = (int)in[0], fi.max_depth = (int)in[1], fi.flags = (int)in[2];
+  fi.tiles_x = (int)in[3], fi.tiles_y = (int)in[4], fi.shard_index = (int)in[5], fi.shard_count = (int)in[6];
+  fi.variant = (int)in[7];
+  fi.record_bytes = (uint64_t)in[8];
+  fi.has_wide4 = in[9] != 0;
+  fi.alone = in[10] != 0;
+  const rt::FramePlan p = rt::plan_frame(fi);
+  const int32_t o[14] = {p.kernel, p.trav, p.needs_variants, p.grid, (int32_t)p.units, p.depth, p.l2_resident, p.xcd_remap,
+                         p.writes_wave_stats, p.lpt, p.split_ceiling, p.rotate_bands, p.pipeline_buffers, p.full_small_build};
+  memcpy(out, o, sizeof o);
   return RT_OK;
 }
 

@@ -58,6 +58,46 @@ inline uint64_t record_layout(uint64_t n_nodes, uint64_t n_tris, uint64_t n_wide
   return wb + wide_bytes;
 }
 
+// Traversal flavours: binary nodes with the LDS wave stack (the product), and the A/B flavours of
+// rt_variants.hip (binary nodes with a VGPR-lane stack, the quantised 4-wide nodes, per-lane walks)
+enum { TRAV_B2_VGPR = 0, TRAV_B2_LDS = 1, TRAV_W4 = 2, TRAV_LANE = 3 };
+
+// Kernel-variant bits (rt_debug_set_variant, or the debug knob RT_KERNEL_VARIANT; for A/B measurements, 0 =
+// the measured-best default: binary nodes + LDS stack, PRIMARY as the fused kernel, FULL as one kernel
+// (k_render_full) at the occupancy its scene size selects). The values are ABI (rt_api.h lists them).
+// rt_dispatch.h plan_frame is the one place that turns them into a frame's kernel and block order.
+enum VariantBit : int {
+  VB_VGPR_STACK = 1,             // binary nodes + lane-register (VGPR) stack
+  VB_WIDE4 = 2,                  // 4-wide quantised nodes (when the scene has them)
+  VB_XCD_ORDER = 4,              // XCD-contiguous tile order
+  VB_FULL_PIPELINE = 16,         // FULL as the stage pipeline (k_full_*) instead of one kernel; with it, per-lane
+  VB_PIPE_LANE_REFL = 32,        //   traversal for the reflection rays,
+  VB_PIPE_LANE_SHADOW1 = 64,     //   the shadow rays of reflection hits,
+  VB_PIPE_LANE_SHADOW0 = 128,    //   the shadow rays of primary hits
+  VB_TWO_RAYS_PER_LANE = 256,    // two rays per lane (PRIMARY)
+  VB_XCD_RUNS_4 = 512,           // block runs of 4 / 16 / plain dispatch order instead of the default 64-block
+  VB_XCD_RUNS_16 = 1024,         //   runs per XCD (a two-bit field)
+  VB_DISPATCH_ORDER = 1536,
+  VB_PERSISTENT = 2048,          // persistent-threads PRIMARY traversal with per-XCD work counters
+  VB_PERSISTENT_NO_STEAL = 4096, //   ... without stealing
+  VB_FULL_8_WAVES = 8192,        // the FULL megakernel's 8-wave / small-scene (6-wave) build regardless of the
+  VB_FULL_SMALL_BUILD = 16384,   //   scene size (the wave split of lone frames follows the build)
+  VB_SPLIT_PRIMARY = 32768,      // PRIMARY as trace + shade kernels instead of the fused k_primary_fused
+  VB_GENERIC_DEPTH = 65536,      // the generic traceRay kernel (k_render_depth) also at the modes' own depths
+  VB_NO_LPT = 131072,            // the default chunked-XCD dispatch order instead of longest-first (k_order_lpt)
+  VB_COARSE_COST_BUCKETS = 262144,  // longest-first with half as many cost buckets (2 per octave: coarser, more
+                                    // spatial order kept)
+  VB_LPT_IN_FLIGHT = 524288,     // longest-first also while other frames are in flight (A/B only: frames that
+                                 // overlap share one map and may read an order mid-rewrite)
+  VB_DUAL_CHAIN = 1048576,       // PRIMARY with two packets per wave (k_primary_dual)
+  VB_PRIMARY_BINARY_TREE = 2097152,  // PRIMARY packets on the binary tree instead of the fp32 4-wide tree
+                                     // (traverse_wide_fast)
+  // PRIMARY variants that leave the fused kernel
+  VB_PRIMARY_UNFUSED = VB_SPLIT_PRIMARY | VB_TWO_RAYS_PER_LANE | VB_PERSISTENT,
+  // bits under which VB_DUAL_CHAIN is ignored
+  VB_DUAL_EXCLUDED = VB_VGPR_STACK | VB_WIDE4 | VB_XCD_ORDER | VB_PRIMARY_UNFUSED | VB_GENERIC_DEPTH,
+};
+
 RT_HD bool is_leaf(uint32_t h) { return (h & kLeafBit) != 0; }
 RT_HD uint32_t leaf_first(uint32_t h) { return h & kLeafFirstMask; }
 RT_HD uint32_t leaf_count(uint32_t h) { return ((h >> kLeafCountShift) & 15u) + 1u; }
@@ -244,7 +284,6 @@ struct FrameParams {
   // wave's neighbourhood maximum; null = off
   uint32_t* cost_dil;
   int32_t dil_r;
-  int32_t dil_w;  // the ring's cost = cost - (cost >> dil_w)
   // pred: each wave raises cost_dil around the wave where its primary hit point is expected in the next frame
   // instead of around itself (rt_kernels.h pred_mark / wave_clock_end): pred_proj = (a, b, c, e), a pixel's
   // view-space ray direction (a px + b, c py + e, -1); pred_step = the camera's last step as a view-space

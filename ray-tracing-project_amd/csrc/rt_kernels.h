@@ -25,6 +25,7 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "rt_kat.h"
@@ -910,10 +911,6 @@ __device__ __forceinline__ void traverse_wide_fast(const DevScene& P, const Ray&
   if (!ANY && !active) h.t = INFINITY;
 }
 
-// Traversal flavours: binary nodes with the LDS wave stack (the product), and the A/B flavours of
-// rt_variants.hip (binary nodes with a VGPR-lane stack, the quantised 4-wide nodes, per-lane walks)
-enum { TRAV_B2_VGPR = 0, TRAV_B2_LDS = 1, TRAV_W4 = 2, TRAV_LANE = 3 };
-
 template <int TRAV, bool STATS>
 struct WaveLds {
   // binary LDS-stack kernels also run the fp32 4-wide loops (traverse_wide*): kStackW entries
@@ -1338,16 +1335,15 @@ __device__ __forceinline__ void wave_clock_end(const FrameParams& P, const uint3
       }
     }
     // the waves the 8 x 8 footprint at (ox, oy) overlaps (1 x 1 at the wave's own position, up to 2 x 2 when
-    // predicted) take its full cost, a ring of r waves around them 3/4 of it (dil_w: the ring's shift, 2 = 3/4, 1 =
-    // 1/2): where the camera stands still the costliest waves still rank first (and take the split), where it
-    // moves their neighbours rank next
+    // predicted) take its full cost, a ring of r waves around them 3/4 of it: where the camera stands still the
+    // costliest waves still rank first (and take the split), where it moves their neighbours rank next
     const int x0 = (int)floorf(ox * 0.125f), y0 = (int)floorf(oy * 0.125f);
     const int fw = ox * 0.125f != (float)x0 ? 2 : 1, fh = oy * 0.125f != (float)y0 ? 2 : 1;
     const int dw = fw + 2 * r, dh = fh + 2 * r;
     if (lane < dw * dh) {
       const int i = lane % dw, j = lane / dw, x = x0 - r + i, y = y0 - r + j;
       const bool inner = i >= r && i < r + fw && j >= r && j < r + fh;
-      const uint32_t v = inner ? c : c - (c >> late_kernarg<int32_t>(offsetof(FrameParams, dil_w)));
+      const uint32_t v = inner ? c : c - (c >> 2);
       if (x >= 0 && y >= 0 && x < 2 * tx && y < 2 * ty)
         atomicMax(dil + 4 * ((y >> 1) * tx + (x >> 1)) + (y & 1) * 2 + (x & 1), v);
     }
@@ -1471,7 +1467,7 @@ __global__ __launch_bounds__(256) void k_shade_primary(FrameParams P) {
 }
 
 
-// PRIMARY as one kernel (default; variant bit 32768 selects the two-kernel form k_trace_primary +
+// PRIMARY as one kernel (default; variant VB_SPLIT_PRIMARY selects the two-kernel form k_trace_primary +
 // k_shade_primary): the traversal, then the shading of the same lane -- the hit record stays in
 // registers instead of a round trip through HBM, and the traversal state is dead by then, so the
 // shading's registers do not add to the traversal's. Resources of the shipped instantiation
@@ -1612,7 +1608,6 @@ __device__ __forceinline__ f3 trace_full(const FrameParams& P, const Ray& r, boo
 #define RT_FULL_WPE_SMALL 6
 #endif
 constexpr int kFullWavesPerEu = 8, kFullWavesPerEuSmall = RT_FULL_WPE_SMALL;
-constexpr size_t kFullSmallSceneBytes = 32u << 20;  // 8 XCDs x 4 MiB L2
 // waves per block of the FULL megakernel (1: one 8x8 wave per block, measured +6.5% on bunny FULL and +8%
 // on the soup over 4 = one 16x16 tile per block)
 constexpr int kFullWPB = 1;
@@ -1841,10 +1836,10 @@ enum RayQuery { Q_CLOSEST = 0, Q_SHADOW = 1, Q_COLOR = 2 };  // rt_trace_closest
 enum VariantOp {
   VOP_TRACE_PRIMARY = 0,  // k_trace_primary with a non-default traversal flavour (c.trav)
   VOP_RENDER_FULL,        // k_render_full with a non-default traversal flavour
-  VOP_FULL_PIPELINE,      // the FULL stage pipeline (variant bit 16; 32 / 64 / 128 per-lane stages)
-  VOP_PRIMARY_DUAL,       // two 8x8 packets per wave (variant bit 1048576)
-  VOP_PRIMARY_X2,         // two rays per lane (variant bit 256)
-  VOP_PRIMARY_PERSISTENT, // persistent threads (variant bit 2048; 4096: no stealing)
+  VOP_FULL_PIPELINE,      // the FULL stage pipeline (VB_FULL_PIPELINE; VB_PIPE_LANE_* per-lane stages)
+  VOP_PRIMARY_DUAL,       // two 8x8 packets per wave (VB_DUAL_CHAIN)
+  VOP_PRIMARY_X2,         // two rays per lane (VB_TWO_RAYS_PER_LANE)
+  VOP_PRIMARY_PERSISTENT, // persistent threads (VB_PERSISTENT; VB_PERSISTENT_NO_STEAL)
   VOP_RAYS,               // ray-list queries with a non-default traversal flavour
 };
 struct VariantCall {
@@ -1859,5 +1854,15 @@ struct VariantCall {
 };
 int variant_launch(int op, const VariantCall& c);
 bool variants_linked();
+
+// Runtime bools as template arguments: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}),
+// so one generic lambda per kernel picks its <STATS, HITS, ...> instantiation.
+template <class F>
+void with_bools(F&& f) { f(); }
+template <class F, class... Bools>
+void with_bools(F&& f, bool b, Bools... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
 
 }  // namespace rt

@@ -394,7 +394,7 @@ __device__ __forceinline__ void traverse_lane(const DevScene& P, const Ray& r, b
 }
 
 
-// Persistent-threads form of k_trace_primary (A/B variant bit 2048): one launch of as many one-wave
+// Persistent-threads form of k_trace_primary (A/B variant VB_PERSISTENT): one launch of as many one-wave
 // blocks as the device holds at 8 waves per SIMD; each wave repeatedly takes the next 8x8 work item
 // from its XCD's counter (XCD x owns items [x Q/8, (x+1) Q/8) of the shard's Q = 4 * tiles items, so
 // an XCD works through a contiguous band of tiles) and, once that range is exhausted, from the other
@@ -839,17 +839,17 @@ static void launch_refl(const FrameParams& P, int g, hipStream_t st, int trav) {
 }
 
 // traversal per FULL stage: packets for the coherent primary rays, per-lane walks for the rest unless
-// the variant knob says otherwise (32: reflection, 64: shadows of reflection hits, 128: shadows of
-// primary hits use packets when set... see kernel_variant)
+// the variant knob says otherwise (VB_PIPE_LANE_REFL: reflection, _SHADOW1: shadows of reflection hits,
+// _SHADOW0: shadows of primary hits)
 template <bool STATS>
 static void launch_full_pipeline(const FrameParams& P, int grid, hipStream_t st, int trav, int variant, bool hits,
                                  hipEvent_t ev_m) {
   const int q0 = 4 * grid;                    // primary waves (wcount0 entries)
   const int lgrid = (P.W * P.H + 255) / 256;  // list kernels: worst case, every pixel listed
   const int q1 = 4 * lgrid;                   // list waves (wcount1 entries)
-  const int t_refl = (variant & 32) ? TRAV_LANE : trav;
-  const int t_sh1 = (variant & 64) ? TRAV_LANE : trav;
-  const int t_sh0 = (variant & 128) ? TRAV_LANE : trav;
+  const int t_refl = (variant & VB_PIPE_LANE_REFL) ? TRAV_LANE : trav;
+  const int t_sh1 = (variant & VB_PIPE_LANE_SHADOW1) ? TRAV_LANE : trav;
+  const int t_sh0 = (variant & VB_PIPE_LANE_SHADOW0) ? TRAV_LANE : trav;
   launch_trace_v<STATS>(P, grid, st, trav);  // + wcount0
   hipLaunchKernelGGL(k_scan_counts, dim3(1), dim3(1024), 0, st, (const uint32_t*)P.wcount0, P.woff0, q0, P.counters + 0);
   hipLaunchKernelGGL(k_full_gen0, dim3(grid), dim3(256), 0, st, P);  // state0, refl, list0
@@ -859,8 +859,7 @@ static void launch_full_pipeline(const FrameParams& P, int grid, hipStream_t st,
   hipLaunchKernelGGL(k_full_gen1, dim3(lgrid), dim3(256), 0, st, P);  // state1, list1
   launch_shadow<STATS>(P, lgrid, st, t_sh1, 1);
   (void)hipEventRecord(ev_m, st);
-  if (hits) hipLaunchKernelGGL(k_full_final<true>, dim3(grid), dim3(256), 0, st, P);
-  else hipLaunchKernelGGL(k_full_final<false>, dim3(grid), dim3(256), 0, st, P);
+  with_bools([&](auto H) { hipLaunchKernelGGL(k_full_final<H.value>, dim3(grid), dim3(256), 0, st, P); }, hits);
 }
 
 
@@ -870,26 +869,18 @@ int variant_launch(int op, const VariantCall& c) {
   const FrameParams& P = c.P;
   switch (op) {
     case VOP_TRACE_PRIMARY:
-      if (c.stats) launch_trace_v<true>(P, c.grid, c.st, c.trav);
-      else launch_trace_v<false>(P, c.grid, c.st, c.trav);
+      with_bools([&](auto S) { launch_trace_v<S.value>(P, c.grid, c.st, c.trav); }, c.stats);
       break;
     case VOP_RENDER_FULL:
-      if (c.stats) { if (c.hits) launch_full_v<true, true>(P, c.grid, c.st, c.trav); else launch_full_v<true, false>(P, c.grid, c.st, c.trav); }
-      else { if (c.hits) launch_full_v<false, true>(P, c.grid, c.st, c.trav); else launch_full_v<false, false>(P, c.grid, c.st, c.trav); }
+      with_bools([&](auto S, auto H) { launch_full_v<S.value, H.value>(P, c.grid, c.st, c.trav); }, c.stats, c.hits);
       break;
     case VOP_FULL_PIPELINE:
-      if (c.stats) launch_full_pipeline<true>(P, c.grid, c.st, c.trav, c.variant, c.hits, c.ev_m);
-      else launch_full_pipeline<false>(P, c.grid, c.st, c.trav, c.variant, c.hits, c.ev_m);
+      with_bools([&](auto S) { launch_full_pipeline<S.value>(P, c.grid, c.st, c.trav, c.variant, c.hits, c.ev_m); }, c.stats);
       break;
     case VOP_PRIMARY_DUAL: {
       const dim3 g((unsigned)c.units), b(64);
-      if (c.boxcol) {
-        if (c.hits) hipLaunchKernelGGL((k_primary_dual<true, true>), g, b, 0, c.st, P);
-        else hipLaunchKernelGGL((k_primary_dual<false, true>), g, b, 0, c.st, P);
-      } else {
-        if (c.hits) hipLaunchKernelGGL((k_primary_dual<true, false>), g, b, 0, c.st, P);
-        else hipLaunchKernelGGL((k_primary_dual<false, false>), g, b, 0, c.st, P);
-      }
+      with_bools([&](auto H, auto B) { hipLaunchKernelGGL((k_primary_dual<H.value, B.value>), g, b, 0, c.st, P); }, c.hits,
+                 c.boxcol);
       break;
     }
     case VOP_PRIMARY_X2:
@@ -899,9 +890,9 @@ int variant_launch(int op, const VariantCall& c) {
       int cus = 0;
       HIPCHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c.device));
       const int waves = std::min(4 * c.grid, std::max(8, cus * 4 * kTraceWavesPerEu));
-      // 4096: no stealing (each XCD's waves finish its own range; needs every XCD to get waves)
+      // VB_PERSISTENT_NO_STEAL: each XCD's waves finish its own range (needs every XCD to get waves)
       hipLaunchKernelGGL(k_trace_primary_persistent, dim3(std::max(waves, 8)), dim3(64), 0, c.st, P, c.queue,
-                         (c.variant & 4096) ? 0u : 7u);
+                         (c.variant & VB_PERSISTENT_NO_STEAL) ? 0u : 7u);
       break;
     }
     case VOP_RAYS:

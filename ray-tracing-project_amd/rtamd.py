@@ -34,7 +34,7 @@ EXPORTS = [
     "rt_trace_closest_normal", "rt_trace_color", "rt_debug_ray", "rt_version_string", "rt_source_hash",
     "rt_debug_timeline", "rt_debug_counters", "rt_box_colors_random", "rt_scene_set_box_colors", "rt_frame_shard_tiles",
     "rt_debug_record_layout", "rt_debug_scene_flags", "rt_debug_env_knobs", "rt_debug_tree_cost",
-    "rt_synchronize_devices", "rt_debug_lpt_stats", "rt_debug_wave_stats",
+    "rt_synchronize_devices", "rt_debug_lpt_stats", "rt_debug_wave_stats", "rt_debug_frame_plan",
 ]
 RT_MAX_DEVICES = 16
 RT_DEVICES_ALL = -1
@@ -156,6 +156,8 @@ def lib():
         L.rt_debug_timeline.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
         L.rt_debug_counters.argtypes = [vp, C.c_int64, C.POINTER(C.c_int64)]
         # (earlier API 4 builds, loaded for A/B through RTAMD_LIB, lack these)
+        if hasattr(L, "rt_debug_frame_plan"):
+            L.rt_debug_frame_plan.argtypes = [vp, C.c_int32, vp, C.c_int32]
         if hasattr(L, "rt_debug_lpt_stats"):
             L.rt_debug_lpt_stats.argtypes = [vp, C.POINTER(C.c_int64)]
         if hasattr(L, "rt_debug_wave_stats"):
@@ -560,6 +562,19 @@ def record_layout(n_nodes, n_tris, n_wide):
     out = np.zeros(2, np.int64)
     check(lib().rt_debug_record_layout(n_nodes, n_tris, n_wide, _p(out)))
     return int(out[0]), int(out[1])
+
+
+FRAME_PLAN_FIELDS = ("kernel", "trav", "needs_variants", "grid", "units", "depth", "l2_resident", "xcd_remap",
+                     "writes_wave_stats", "lpt", "split_ceiling", "rotate_bands", "pipeline_buffers", "full_small_build")
+
+
+def frame_plan(mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_count, variant, record_bytes, has_wide4, alone):
+    """rt_debug_frame_plan: the dispatch plan of such a frame as a dict of ints (no device needed)."""
+    inp = np.array([mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_count, variant, record_bytes,
+                    int(has_wide4), int(alone)], np.int64)
+    out = np.zeros(len(FRAME_PLAN_FIELDS), np.int32)
+    check(lib().rt_debug_frame_plan(_p(inp), len(inp), _p(out), len(out)))
+    return dict(zip(FRAME_PLAN_FIELDS, out.tolist()))
 
 
 def flycam(W, H, dx=0.0, dy=0.0, dz=0.0):

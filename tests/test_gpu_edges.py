@@ -15,12 +15,14 @@ import pytest
 
 import edge_scenes as E
 from conftest import PARITY_REPORT, scene_path
+from kernel_variants import VARIANTS
 from test_gpu_parity import TOL, compare
 from test_oracle_pinning import same_bits
 
 pytestmark = pytest.mark.gpu
 
-PRODUCT_VARIANTS = [2097152, 262144, 65536, 32768, 1536, 8192, 16384]
+PRODUCT_VARIANTS = [VARIANTS[n] for n in ("primary-binary-tree", "coarse-cost-buckets", "generic-depth-kernel", "split-primary",
+                                           "dispatch-order", "full-8-waves", "full-small-build")]
 FRAME_SIZES = [(37, 11), (65, 9), (64, 40)]
 TIE_CAMERA = (3.0, -2.0, 20.0)  # flycam(W, H, dx, dy, dz): the triple plane nearly head-on from z = 1
 

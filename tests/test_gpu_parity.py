@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, scene_path
+from kernel_variants import VARIANTS, VARIANTS_LIB
 from test_oracle_pinning import colour_errors, read_kat, same_bits
 
 pytestmark = pytest.mark.gpu
@@ -198,16 +199,6 @@ def test_stats_counting_run(rt, soup):
     assert st["primary_rays"] == W * H
     assert st["node_visits"] > W * H and st["tri_tests"] > W * H
     assert st["wave_node_fetches"] * 16 < st["node_visits"]  # coherence: one fetch serves many rays
-
-
-# variant bits the product library serves itself (rt_api.h rt_debug_set_variant)
-VARIANTS = {"xcd-order": 4, "xcd-runs-4": 512, "dispatch-order": 1536, "full-8-waves": 8192, "full-small-build": 16384,
-            "split-primary": 32768, "generic-depth-kernel": 65536, "coarse-cost-buckets": 262144,
-            "primary-binary-tree": 2097152}
-# the A/B kernels of the variants library only (rt_variants.hip, `make variants`)
-VARIANTS_LIB = {"vgpr-stack": 1, "wide4": 2, "full-pipeline": 16, "pipeline-lane-refl": 48,
-                "pipeline-lane-all": 16 | 32 | 64 | 128, "two-rays-per-lane": 256, "persistent": 2048,
-                "persistent-no-steal": 2048 | 4096, "dual-chain": 1048576}
 
 
 def variant_frames_identical(rt, scenes, bits, extra=()):

@@ -14,7 +14,8 @@ sys.path.insert(0, HERE)
 import conftest  # noqa: E402  (loads ray-tracing-project_amd/rtamd.py, honouring RTAMD_LIB)
 import edge_scenes  # noqa: E402
 from conftest import scene_path  # noqa: E402
-from test_gpu_parity import VARIANTS_LIB, variant_frames_identical  # noqa: E402
+from kernel_variants import VARIANTS_LIB  # noqa: E402
+from test_gpu_parity import variant_frames_identical  # noqa: E402
 
 
 def main():

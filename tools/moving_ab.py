@@ -27,7 +27,7 @@ reps = int(sys.argv[5]) if len(sys.argv) > 5 else 2
 env = {"moved0": {"RT_LPT_MOVED": "0"}, "moved1": {"RT_LPT_MOVED": "1"}, "r1": {"RT_LPT_REFRESH": "1"},
        "dil0": {"RT_LPT_DILATE": "0"}, "dil1": {"RT_LPT_DILATE": "1"}, "dil2": {"RT_LPT_DILATE": "2"},
        "nopred": {"RT_LPT_PRED": "0"}, "exact": {"RT_LPT_DILATE": "0", "RT_LPT_PRED": "0"}}.get(policy, {})
-if policy.startswith("env:"):  # any debug knobs, e.g. env:RT_SPLIT_KP_ANY=1,RT_LPT_MOVED=1
+if policy.startswith("env:"):  # any debug knobs, e.g. env:RT_SPLIT_KP=512,RT_LPT_MOVED=1
     env = dict(kv.split("=", 1) for kv in policy[4:].split(","))
 os.environ.update(env)
 rt = bench.load_rtamd()

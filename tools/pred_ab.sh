@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export MNOR05=1
 P="env:RT_LPT_MOVED=1,RT_LPT_PRED=1"
-MSCENES=${MSCENES:-"bunny:full bunny:primary soup:primary"} MPOLICIES=${MPOLICIES:-"lib $P $P,RT_LPT_DILATE=1 $P,RT_LPT_DILW=1 $P,RT_LPT_DILATE=1,RT_LPT_DILW=1 $P,RT_LPT_DILATE=0"} \
+MSCENES=${MSCENES:-"bunny:full bunny:primary soup:primary"} MPOLICIES=${MPOLICIES:-"lib $P $P,RT_LPT_DILATE=1 $P,RT_LPT_DILATE=0"} \
   bash tools/gpu_round6.sh $TAG moving || exit $?
 [ -n "${NOSTATIC:-}" ] && exit 0
 for rep in 1 2; do
