@@ -35,6 +35,10 @@ $(OBJ)/rt_variants.o: $(PKG)/csrc/rt_variants.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+$(OBJ)/rt_rays.o: $(PKG)/csrc/rt_rays.hip $(HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c $< -o $@
+
 $(OBJ)/rt_build.o: $(PKG)/csrc/rt_build.hip $(HDRS)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c $< -o $@
@@ -50,7 +54,7 @@ $(OBJ)/rt_cache.o: $(PKG)/csrc/rt_cache.cpp $(HDRS)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-PRODUCT_OBJS := $(OBJ)/rt_device.o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
+PRODUCT_OBJS := $(OBJ)/rt_device.o $(OBJ)/rt_rays.o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
 $(LIB): $(PRODUCT_OBJS)
 	@mkdir -p $(PKG)/lib
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -lpthread
@@ -65,11 +69,12 @@ $(VARLIB): $(PRODUCT_OBJS) $(OBJ)/rt_variants.o
 
 # A/B builds of the same sources with extra device flags (experiments only):
 #   make ablib TAG=noslp EXTRA="-fno-slp-vectorize"  ->  lib/librtamd_noslp.so  (select with RTAMD_LIB)
-ablib: $(PKG)/csrc/rt_device.hip $(HDRS) $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
+ablib: $(PKG)/csrc/rt_device.hip $(PKG)/csrc/rt_rays.hip $(HDRS) $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
 	@mkdir -p $(OBJ) $(PKG)/lib
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $< -o $(OBJ)/rt_device_$(TAG).o
+	$(HIPCC) $(HIPFLAGS) $(EXTRA) -Wno-unused-result -c $(PKG)/csrc/rt_rays.hip -o $(OBJ)/rt_rays_$(TAG).o
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $(PKG)/csrc/rt_variants.hip -o $(OBJ)/rt_variants_$(TAG).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(OBJ)/rt_device_$(TAG).o $(OBJ)/rt_variants_$(TAG).o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(OBJ)/rt_device_$(TAG).o $(OBJ)/rt_rays_$(TAG).o $(OBJ)/rt_variants_$(TAG).o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o -lpthread
 
 # debug build of the same sources with every scalar prefetch offset checked on the device (RT_CHECK_PREFETCH:
 # an out-of-range offset is recorded and fails the next rt_synchronize) -> lib/librtamd_pfcheck.so,

@@ -374,6 +374,76 @@ int rt_trace_closest_normal(rt_scene* s, int32_t n, const float* o3, const float
 int rt_trace_color(rt_scene* s, int32_t n, const float* o3, const float* d3, const rt_light* lights, int32_t n_lights,
                    float* rgb3, int32_t* face, float* t);
 
+/* ---------------------------------------------------------------------------------------------
+ * Ray streams: the same three queries on ray lists that already live in device memory, enqueued on the
+ * caller's stream (feature test: RT_HAS_RAY_STREAMS; the API version stays 4).
+ *
+ * rt_trace_stream(s, query, flags, rays, lights, n_lights, hip_stream)
+ *   query       RT_RAYS_CLOSEST = rt_trace_closest_normal, RT_RAYS_SHADOW = rt_trace_shadow, RT_RAYS_COLOR =
+ *               rt_trace_color; the values written are exactly the host-pointer call's (a miss: face -1,
+ *               t +inf, P and N zero). Nothing is written at index n or beyond.
+ *   rays        every pointer is device (or managed) memory of the scene's device -- devices[0] of a
+ *               multi-device scene -- e.g. a torch tensor's data_ptr(). a3 / b3 are read, the outputs the
+ *               query names are written: CLOSEST face and t (required), P3 and N3 (optional); SHADOW blocked
+ *               (required); COLOR rgb3 (required), face and t (optional). lights / n_lights: COLOR only,
+ *               host memory, as rt_trace_color.
+ *   hip_stream  non-NULL: the caller's hipStream_t (torch: torch.cuda.current_stream().cuda_stream). All work
+ *               is enqueued there in order and the call returns without waiting; nothing in it synchronises
+ *               the device except a growth of the reorder scratch. NULL: the scene's own stream, and the call
+ *               returns after completion, as the host-pointer calls do.
+ *   flags       RT_RAYS_REORDER: trace the rays in coherence order instead of list order. Each ray gets a
+ *               32-bit key on the device (its origin's cell in the scene's bounds, its direction's octant
+ *               and cell; csrc/rt_raykey.h), the (key, index) pairs are radix-sorted, and packet lanes take
+ *               their rays through that permutation, writing each result at its ray's own index. A ray's
+ *               result never depends on the rays sharing its wave, so every output bit equals the in-order
+ *               call's; what changes is how many node records the waves fetch. Opt-in: the key and sort
+ *               cost time that only an unordered list pays back (README.md has the measured figures).
+ *               Lists of at most 64 rays are one packet and are traced as given. The scratch (16 B per ray
+ *               plus the sort's temporary storage, about 32 B per ray together) belongs to the scene, grows
+ *               geometrically -- the one place a call may hipMalloc / hipFree and so stall -- and is freed
+ *               with the scene. Calls on different streams are ordered on it by an event: the later stream
+ *               waits for the earlier call's use. One host thread per scene, as everywhere.
+ *               RT_RAYS_STATS: a counting run (slower): clears the scene's counters, then counts node visits,
+ *               triangle tests and the per-wave node / triangle record fetches (rt_debug_counters slots
+ *               0..3; 4 rays, 5 hits). Not available with the 4-wide A/B variant (RT_ERR_UNSUPPORTED).
+ *   Checked before anything is enqueued: query and flags, n >= 0, the query's required outputs (n > 0), the
+ *   lights, and every non-NULL pointer's memory (hipPointerGetAttributes: host memory or another device's
+ *   returns RT_ERR_INVALID). n == 0 returns RT_OK and launches nothing. A host-only scene or a machine
+ *   without a GPU returns RT_ERR_NO_DEVICE.
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_RAY_STREAMS 1
+enum { RT_RAYS_CLOSEST = 0, RT_RAYS_SHADOW = 1, RT_RAYS_COLOR = 2 };
+#define RT_RAYS_REORDER 1   /* trace in coherence order (results identical; needs scratch ~32 B/ray) */
+#define RT_RAYS_STATS   2   /* counting run (slower): fills the scene's counters, read with rt_debug_counters */
+
+typedef struct rt_ray_stream {      /* every pointer: device memory on the scene's device (devices[0]) */
+  int32_t n;
+  const float* a3;                  /* CLOSEST/COLOR: origins [n][3];  SHADOW: P [n][3] */
+  const float* b3;                  /* CLOSEST/COLOR: directions;      SHADOW: L */
+  int32_t* face; float* t;          /* CLOSEST (both required), COLOR (optional) */
+  float* P3; float* N3;             /* CLOSEST, optional */
+  int32_t* blocked;                 /* SHADOW, required */
+  float* rgb3;                      /* COLOR, required */
+} rt_ray_stream;
+
+int rt_trace_stream(rt_scene* s, int32_t query, int32_t flags, const rt_ray_stream* rays,
+                    const rt_light* lights, int32_t n_lights, void* hip_stream);
+/* The primary rays of a width x height frame of cam as a device ray list: pixel (px, py) at index
+ * py * width + px, exactly the origin and direction the frame kernels trace for it (traceRayThread,
+ * flyscene.cpp:301-308). Both outputs [width * height][3], device memory, checked and enqueued as above. */
+int rt_rays_camera(rt_scene* s, const rt_camera* cam, int32_t width, int32_t height,
+                   float* origins3_device, float* dirs3_device, void* hip_stream);
+/* The grid of the coherence keys: the world bounds of the scene's vertices (lo xyz, hi xyz). Host data. */
+int rt_scene_ray_bounds(rt_scene* s, float bounds6[6]);
+/* The keys RT_RAYS_REORDER gives n rays on a grid of bounds6, computed on the host by the function the device
+ * runs (tests and diagnostics). Bit 31: a NaN / infinite component or an all-zero direction (sorted last). */
+int rt_debug_ray_keys(int32_t query, int32_t n, const float* a3, const float* b3,
+                      const float bounds6[6], uint32_t* keys_out);           /* host only, no device */
+/* The order of the scene's last RT_RAYS_REORDER call: perm_out[k] = the index of the ray traced k-th (the
+ * identity for a list of at most 64 rays); *n_out = that call's n. capacity smaller than n: RT_ERR_INVALID.
+ * Waits for that call. */
+int rt_debug_ray_order(rt_scene* s, int64_t capacity, uint32_t* perm_out, int64_t* n_out); /* last REORDER call */
+
 /* createDebugRay (flyscene.cpp:129-173) without the GL cylinders: the camera ray through a
  * (float) mouse position and its reflection chain, up to max_depth segments; every segment carries the
  * first ray's traceRay colour; a miss ends the chain with a 10-unit segment. *n_out = segments written. */
@@ -447,7 +517,8 @@ int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origi
  * PRIMARY as trace + shade kernels, 65536 the generic traceRay kernel, 131072 / 262144 / 524288
  * longest-first dispatch knobs (524288, longest-first also with frames in flight, is A/B only: the frames share
  * one order, which one of them may read while another's sort rewrites it, and then skip or repeat waves),
- * 2097152 PRIMARY packets on the binary tree. Bits of the variants library
+ * 2097152 PRIMARY packets on the binary tree, 4194304 the origin-major layout of the ray streams' coherence key
+ * (rt_debug_ray_keys follows it). Bits of the variants library
  * only (make variants -> librtamd_variants.so; the product library's rt_render returns
  * RT_ERR_UNSUPPORTED for them): 1 VGPR wave stack, 2 4-wide quantised BVH (scenes of the host builders,
  * which also build that tree), 16 FULL as a stage pipeline (whole frames only: a sharded frame returns

@@ -1,8 +1,8 @@
 // rt_device.hip -- the product library's gfx950 kernels and device-side C ABI of the MI355X ray-traversal
 // library. The device code of the hot path is rt_kernels.h (shared with the A/B variants of
 // rt_variants.hip); this file instantiates the product kernels, holds the non-template kernels (dispatch
-// order, box colours, output path, known-answer tests) and the host glue (scene upload, frame dispatch,
-// ray-list queries).
+// order, box colours, output path, known-answer tests) and the host glue (scene upload, frame dispatch).
+// The ray-list queries (host-pointer and device-resident) are rt_rays.hip.
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -714,6 +714,7 @@ void device_release(rt_scene* s) {
   (void)hipSetDevice(s->device);
   for (int k = 0; k < s->n_slots; k++)
     if (s->slots[k].stream) (void)hipStreamSynchronize((hipStream_t)s->slots[k].stream);
+  ray_stream_release(s);  // the reorder scratch and its event (rt_rays.hip)
   void* bufs[] = {s->d_nodes, s->d_nodes4, s->d_fshade, s->d_refbox, s->d_mats, s->d_stats,
                   s->d_face_boxcolor, s->asm_buf.d_pack, s->d_pf_check};  // d_tris: inside d_nodes
   for (void* b : bufs)
@@ -916,7 +917,7 @@ static int ensure_face_boxcolor(rt_scene* s) {
   return RT_OK;
 }
 
-static void fill_scene_params(const rt_scene* s, FrameParams& P) {
+void fill_scene_params(const rt_scene* s, FrameParams& P) {
   memset(&P, 0, sizeof P);
   const HostScene& hs = s->hs;
   P.sc.nodes = s->d_nodes;
@@ -1004,13 +1005,13 @@ __attribute__((weak)) bool variants_linked() { return false; }
 __attribute__((weak)) int variant_launch(int, const VariantCall&) { return RT_ERR_UNSUPPORTED; }
 
 static std::atomic<int> g_variant{0};  // rt_debug_set_variant(), or RT_KERNEL_VARIANT once rt_debug_env_knobs(1)
-static int kernel_variant() { return g_variant.load(std::memory_order_relaxed); }
+int kernel_variant() { return g_variant.load(std::memory_order_relaxed); }
 
 }  // namespace rt
 
 using namespace rt;
 
-static int check_device_scene(rt_scene* s) {
+int rt::check_device_scene(rt_scene* s) {
   if (!s) { set_error("null scene"); return RT_ERR_INVALID; }
   if (s->device == RT_DEVICE_NONE) { set_error("scene was created host-only (RT_DEVICE_NONE)"); return RT_ERR_NO_DEVICE; }
   HIPCHECK(hipSetDevice(s->device));
@@ -1101,7 +1102,7 @@ static int check_frame_args(const rt_camera* cam, const rt_light* lights, int32_
 }
 
 // calculateColor's order: point lights first, then directional lights (each in array order)
-static void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights) {
+void rt::fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights) {
   P.n_lights = n_lights;
   int k = 0;
   for (int pass = 0; pass < 2; pass++)
@@ -1116,7 +1117,7 @@ static void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights
 }
 
 // camera (camera.hpp:115-118,155-173,263-266) and lights of a frame; P.Minv is set (fill_scene_params)
-static void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights) {
+void rt::fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights) {
   affinv(cam->view_matrix, P.vinv);
   float L[9], Li[9];
   linear_of(cam->view_matrix, L);
@@ -1436,7 +1437,7 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
 }
 
 // RT_CHECK_PREFETCH debug build: an out-of-range scalar prefetch offset recorded by the kernels fails the call
-static int check_prefetch_word(rt_scene* s) {
+int rt::check_prefetch_word(rt_scene* s) {
 #ifdef RT_CHECK_PREFETCH
   uint32_t w = 0;
   HIPCHECK(hipMemcpy(&w, s->d_pf_check, 4, hipMemcpyDeviceToHost));
@@ -2160,102 +2161,6 @@ extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_light* ligh
     }
   }
   return RT_OK;
-}
-
-// ray-list queries: closest (face, t, P, optional interpolated normal), any-hit (blocked) or colour
-static int trace_rays(rt_scene* s, int query, int32_t n, const float* o, const float* d, int32_t* face, float* t,
-                      float* P3, float* N3, int32_t* blocked, float* rgb, const rt_light* lights, int32_t n_lights) {
-  int rc = check_device_scene(s);
-  if (rc) return rc;
-  if (n < 0 || (n && (!o || !d)) || n_lights < 0 || n_lights > RT_MAX_LIGHTS || (n_lights && !lights)) {
-    set_error("trace: invalid arguments");
-    return RT_ERR_INVALID;
-  }
-  if (n == 0) return RT_OK;
-  FrameParams P;
-  fill_scene_params(s, P);
-  if (query == Q_COLOR) fill_lights(P, lights, n_lights);
-  const size_t n3 = (size_t)n * 12;
-  hipStream_t st = (hipStream_t)s->stream;
-  std::vector<void*> bufs;
-  struct Free {
-    std::vector<void*>& b;
-    ~Free() { for (void* p : b) (void)hipFree(p); }
-  } free_{bufs};
-  auto dalloc = [&](size_t bytes) -> void* {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    bufs.push_back(p);
-    return p;
-  };
-  RayParams R{};
-  R.n = n;
-  float* d_o = (float*)dalloc(n3);
-  float* d_d = (float*)dalloc(n3);
-  if (!d_o || !d_d) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-  HIPCHECK(hipMemcpy(d_o, o, n3, hipMemcpyHostToDevice));
-  HIPCHECK(hipMemcpy(d_d, d, n3, hipMemcpyHostToDevice));
-  R.o = d_o;
-  R.d = d_d;
-  if (query == Q_SHADOW) {
-    if (!(R.blocked = (int32_t*)dalloc((size_t)n * 4))) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-  } else {
-    R.face = (int32_t*)dalloc((size_t)n * 4);
-    R.t = (float*)dalloc((size_t)n * 4);
-    if (!R.face || !R.t) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-    if (query == Q_CLOSEST && P3 && !(R.P = (float*)dalloc(n3))) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-    if (query == Q_CLOSEST && N3 && !(R.N = (float*)dalloc(n3))) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-    if (query == Q_COLOR && !(R.rgb = (float*)dalloc(n3))) { set_error("trace: device allocation failed"); return RT_ERR_NOMEM; }
-  }
-  const int grid = (n + 255) / 256;
-  const bool w4 = pick_trav(kernel_variant(), P.sc.n_nodes4 > 0) == TRAV_W4;
-  if (w4 && !variants_linked()) {
-    set_error("trace: kernel variant %d is an A/B build option, not in this library (make variants)", kernel_variant());
-    return RT_ERR_UNSUPPORTED;
-  }
-  if (w4) {
-    VariantCall vc;
-    vc.P = P, vc.R = R, vc.grid = grid, vc.st = st, vc.query = query;
-    variant_launch(VOP_RAYS, vc);
-  } else if (query == Q_COLOR) {
-    hipLaunchKernelGGL((k_rays_color<TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R);
-  } else {
-    with_bools([&](auto ANY) { hipLaunchKernelGGL((k_rays<ANY.value, TRAV_B2_LDS>), dim3(grid), dim3(256), 0, st, P, R); }, query == Q_SHADOW);
-  }
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(st));
-  if ((rc = check_prefetch_word(s))) return rc;
-  if (query == Q_SHADOW) {
-    HIPCHECK(hipMemcpy(blocked, R.blocked, (size_t)n * 4, hipMemcpyDeviceToHost));
-  } else {
-    if (face) HIPCHECK(hipMemcpy(face, R.face, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (t) HIPCHECK(hipMemcpy(t, R.t, (size_t)n * 4, hipMemcpyDeviceToHost));
-    if (R.P) HIPCHECK(hipMemcpy(P3, R.P, n3, hipMemcpyDeviceToHost));
-    if (R.N) HIPCHECK(hipMemcpy(N3, R.N, n3, hipMemcpyDeviceToHost));
-    if (R.rgb) HIPCHECK(hipMemcpy(rgb, R.rgb, n3, hipMemcpyDeviceToHost));
-  }
-  return RT_OK;
-}
-
-extern "C" int rt_trace_closest(rt_scene* s, int32_t n, const float* o, const float* d, int32_t* face, float* t,
-                                float* P3) {
-  return trace_rays(s, Q_CLOSEST, n, o, d, face, t, P3, nullptr, nullptr, nullptr, nullptr, 0);
-}
-
-extern "C" int rt_trace_closest_normal(rt_scene* s, int32_t n, const float* o, const float* d, int32_t* face, float* t,
-                                       float* P3, float* N3) {
-  return trace_rays(s, Q_CLOSEST, n, o, d, face, t, P3, N3, nullptr, nullptr, nullptr, 0);
-}
-
-extern "C" int rt_trace_shadow(rt_scene* s, int32_t n, const float* P3, const float* L3, int32_t* blocked) {
-  if (!blocked && n > 0) { set_error("rt_trace_shadow: null output"); return RT_ERR_INVALID; }
-  return trace_rays(s, Q_SHADOW, n, P3, L3, nullptr, nullptr, nullptr, nullptr, blocked, nullptr, nullptr, 0);
-}
-
-extern "C" int rt_trace_color(rt_scene* s, int32_t n, const float* o, const float* d, const rt_light* lights,
-                              int32_t n_lights, float* rgb, int32_t* face, float* t) {
-  if (!rgb && n > 0) { set_error("rt_trace_color: null output"); return RT_ERR_INVALID; }
-  return trace_rays(s, Q_COLOR, n, o, d, face, t, nullptr, nullptr, nullptr, rgb, lights, n_lights);
 }
 
 extern "C" int rt_debug_math_device(int32_t op, int32_t n, const float* in, float* out) {

@@ -2709,3 +2709,44 @@ extern "C" int rt_debug_validate_bvh(const rt_scene* s, int64_t info[7]) {
   if (!ok) { rt::set_error("acceleration structure check failed (%lld violations)", (long long)v.bad); return RT_ERR_INVALID; }
   return RT_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Ray streams, host side: the coherence keys (rt_raykey.h, the function k_ray_keys runs) and their grid
+// ------------------------------------------------------------------------------------------------
+#include "rt_raykey.h"
+
+const float* rt::scene_ray_bounds(rt_scene* s) {
+  if (!s->ray_bounds_valid) {
+    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (const rt::f3& v : s->hs.wv) {
+      const float c[3] = {v.x, v.y, v.z};
+      for (int k = 0; k < 3; k++) {  // comparisons: a NaN coordinate leaves both bounds alone
+        if (c[k] < lo[k]) lo[k] = c[k];
+        if (c[k] > hi[k]) hi[k] = c[k];
+      }
+    }
+    for (int k = 0; k < 3; k++) {
+      const bool ok = std::isfinite(lo[k]) && std::isfinite(hi[k]);
+      s->ray_bounds[k] = ok ? lo[k] : 0.0f;
+      s->ray_bounds[3 + k] = ok ? hi[k] : 0.0f;
+    }
+    s->ray_bounds_valid = true;
+  }
+  return s->ray_bounds;
+}
+
+extern "C" int rt_scene_ray_bounds(rt_scene* s, float bounds6[6]) {
+  if (!s || !bounds6) { rt::set_error("rt_scene_ray_bounds: null argument"); return RT_ERR_INVALID; }
+  memcpy(bounds6, rt::scene_ray_bounds(s), 24);
+  return RT_OK;
+}
+
+extern "C" int rt_debug_ray_keys(int32_t query, int32_t n, const float* a3, const float* b3, const float bounds6[6],
+                                 uint32_t* keys_out) {
+  if (query < RT_RAYS_CLOSEST || query > RT_RAYS_COLOR) { rt::set_error("rt_debug_ray_keys: bad query %d", query); return RT_ERR_INVALID; }
+  if (n < 0 || !bounds6 || (n && (!a3 || !b3 || !keys_out))) { rt::set_error("rt_debug_ray_keys: invalid arguments"); return RT_ERR_INVALID; }
+  // every query keys its ray by (a, b): origin and direction, or a shadow ray's P and L
+  const bool origin_major = (rt::kernel_variant() & rt::VB_RAYKEY_ORIGIN_MAJOR) != 0;
+  for (int32_t i = 0; i < n; i++) keys_out[i] = rt::ray_key(a3 + 3 * (size_t)i, b3 + 3 * (size_t)i, bounds6, origin_major);
+  return RT_OK;
+}

@@ -20,6 +20,10 @@ struct uint2 { unsigned int x, y; };
 
 #include "rt_math.h"
 
+struct rt_scene;
+struct rt_light;
+struct rt_camera;
+
 namespace rt {
 
 constexpr uint32_t kLeafBit = 0x80000000u;
@@ -92,6 +96,7 @@ enum VariantBit : int {
   VB_DUAL_CHAIN = 1048576,       // PRIMARY with two packets per wave (k_primary_dual)
   VB_PRIMARY_BINARY_TREE = 2097152,  // PRIMARY packets on the binary tree instead of the fp32 4-wide tree
                                      // (traverse_wide_fast)
+  VB_RAYKEY_ORIGIN_MAJOR = 4194304,  // ray streams: the origin-major key layout instead of octant-major (rt_raykey.h)
   // PRIMARY variants that leave the fused kernel
   VB_PRIMARY_UNFUSED = VB_SPLIT_PRIMARY | VB_TWO_RAYS_PER_LANE | VB_PERSISTENT,
   // bits under which VB_DUAL_CHAIN is ignored
@@ -311,6 +316,18 @@ struct RayParams {
   int32_t* blocked;
   float* N;        // [n][3] interpolated normal at the closest hit (optional)
   float* rgb;      // [n][3] traceRay colour (rt_trace_color)
+  // RT_RAYS_REORDER: lane l of the packet at `base` traces ray perm[base + l] and writes its results at that
+  // index; null = the list as given (one wave-uniform branch)
+  const uint32_t* perm;
 };
+
+// host helpers of rt_device.hip shared with rt_rays.hip
+int check_device_scene(rt_scene* s);  // RT_ERR_NO_DEVICE for a host-only scene; makes the scene's device current
+void fill_scene_params(const rt_scene* s, FrameParams& P);  // clears P, then the scene's part of it
+void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights);
+// camera and lights of a frame; P.Minv is set (fill_scene_params)
+void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights);
+int check_prefetch_word(rt_scene* s);  // RT_CHECK_PREFETCH debug build; RT_OK otherwise
+int kernel_variant();                  // rt_debug_set_variant's current value
 
 }  // namespace rt

@@ -1746,30 +1746,45 @@ void k_render_depth(FrameParams P) {
   wave_clock_end(P, lds.clk, c.lane, c.qw);
 }
 
-template <bool ANY, int TRAV>
+// Ray-list packets (rt_trace_* / rt_trace_stream): wave w of the list traces entries 64 w .. 64 w + 63 -- of the
+// list itself, or of its coherence order R.perm (RT_RAYS_REORDER), each lane then loading the ray perm names and
+// writing that ray's results at its own index. A ray's result is its lane's (t, rank) argmin and never depends
+// on the rays beside it, so any grouping gives the same bits. Inactive tail lanes alias the packet's first ray
+// and write nothing. STATS (RT_RAYS_STATS): the counting loops, flushed into P.stats.
+__device__ __forceinline__ int ray_index(const RayParams& R, int entry) {
+  return R.perm ? (int)R.perm[entry] : entry;
+}
+
+template <bool ANY, int TRAV, bool STATS = false>
 __global__ __launch_bounds__(256) void k_rays(FrameParams P, RayParams R) {
-  __shared__ WaveLds<TRAV, false> lds;
+  __shared__ WaveLds<TRAV, STATS> lds;
   const int lane = threadIdx.x & 63;
   const int base = (int)uniform((blockIdx.x * 4 + (threadIdx.x >> 6)) * 64);
   if (base >= R.n) return;
-  const int i = base + lane;
-  const bool active = i < R.n;
-  const int j = active ? i : base;
+  const bool active = base + lane < R.n;
+  const int i = ray_index(R, active ? base + lane : base);  // the lane's ray: loaded from and written at i
+  uint32_t cnt_[STATS ? ST_COUNT : 1] = {};
+  uint32_t* const cnt = STATS ? cnt_ : nullptr;
   Ray r;
   if (ANY) {  // shadow(P, L): triangle tests from P + 0.003 L, box tests from P (flyscene.cpp:512-519)
-    const f3 p = ld3(R.o + 3 * (size_t)j), L = ld3(R.d + 3 * (size_t)j);
+    const f3 p = ld3(R.o + 3 * (size_t)i), L = ld3(R.d + 3 * (size_t)i);
     r.o = offset(p, L, 0.003f);
     r.d = L;
     r.o2 = affv3(P.Minv, p);
   } else {
-    r.o = ld3(R.o + 3 * (size_t)j);
-    r.d = ld3(R.d + 3 * (size_t)j);
+    r.o = ld3(R.o + 3 * (size_t)i);
+    r.d = ld3(R.d + 3 * (size_t)i);
     r.o2 = affv3(P.Minv, r.o);
   }
   setup_cull(r, P.sc.static_pad);
   Hit h{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
   bool found = false;
-  trace<ANY, false, TRAV>(P.sc, r, active, h, found, lds, (int)uniform(threadIdx.x >> 6), nullptr);
+  if (STATS && active) { cnt[ST_RAYS]++; cnt[ST_TOTAL]++; }
+  trace<ANY, STATS, TRAV>(P.sc, r, active, h, found, lds, (int)uniform(threadIdx.x >> 6), cnt);
+  if (STATS) {
+    if (active && (ANY ? found : h.t != INFINITY)) cnt[ST_HITS]++;
+    flush_stats(P, cnt, lane);
+  }
   if (!active) return;
   if (ANY) {
     R.blocked[i] = found ? 1 : 0;
@@ -1799,24 +1814,27 @@ __global__ __launch_bounds__(256) void k_rays(FrameParams P, RayParams R) {
 }
 
 // traceRay(o, d, 0) (FULL, max_depth 2) for a list of rays (rt_trace_color): colour, first-hit face and t
-template <int TRAV>
+template <int TRAV, bool STATS = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEu)))
 void k_rays_color(FrameParams P, RayParams R) {
-  __shared__ WaveLds<TRAV, false> lds;
+  __shared__ WaveLds<TRAV, STATS> lds;
   const int lane = threadIdx.x & 63, wv = (int)uniform(threadIdx.x >> 6);
   const int base = (int)uniform((blockIdx.x * 4 + (threadIdx.x >> 6)) * 64);
   if (base >= R.n) return;
-  const int i = base + lane;
-  const bool active = i < R.n;
-  const int j = active ? i : base;
+  const bool active = base + lane < R.n;
+  const int i = ray_index(R, active ? base + lane : base);
+  uint32_t cnt_[STATS ? ST_COUNT : 1] = {};
+  uint32_t* const cnt = STATS ? cnt_ : nullptr;
   Ray r;
-  r.o = ld3(R.o + 3 * (size_t)j);
-  r.d = ld3(R.d + 3 * (size_t)j);
+  r.o = ld3(R.o + 3 * (size_t)i);
+  r.d = ld3(R.d + 3 * (size_t)i);
   r.o2 = affv3(P.Minv, r.o);
   setup_cull(r, P.sc.static_pad);
+  if (STATS && active) { cnt[ST_RAYS]++; cnt[ST_TOTAL]++; }
   Hit h;
   uint32_t face0;
-  const f3 col = trace_full<false, TRAV>(P, r, active, lds, wv, nullptr, h, face0);
+  const f3 col = trace_full<STATS, TRAV>(P, r, active, lds, wv, cnt, h, face0);
+  if (STATS) flush_stats(P, cnt, lane);
   if (!active) return;
   R.rgb[3 * (size_t)i + 0] = col.x;
   R.rgb[3 * (size_t)i + 1] = col.y;
@@ -1824,8 +1842,6 @@ void k_rays_color(FrameParams P, RayParams R) {
   if (R.face) R.face[i] = face0 != 0xFFFFFFFFu ? (int32_t)face0 : -1;
   if (R.t) R.t[i] = h.t;
 }
-
-
 
 // ------------------------------------------------------------------------------------------------
 // The A/B kernel variants (RT_KERNEL_VARIANT bits, rt_debug_set_variant) live in rt_variants.hip and are

@@ -251,6 +251,21 @@ struct rt_scene {
   int64_t rays_key[4] = {-1, -1, -1, -1}, rays_of_key = 0;  // primary rays of a frame shape (W, H, shard)
   int64_t last_timeline_waves = 0;  // waves recorded by the last RT_FRAME_TIMELINE frame
   int64_t last_wave_stats_waves = 0;  // logical waves of the last RT_FRAME_WAVE_STATS frame
+  // Ray streams (rt_rays.hip): the scratch of RT_RAYS_REORDER -- per ray its key and index, in and out of the radix
+  // sort (4 x 4 B), plus the sort's own temporary storage. Grown geometrically, freed with the scene. `ev` is
+  // recorded after each use on `last_stream`; a call on another stream waits on it first.
+  struct RayScratch {
+    uint32_t* d_buf = nullptr;   // [4][capacity]: keys in, keys out, indices in, indices out (the permutation)
+    size_t capacity = 0;         // rays
+    void* d_tmp = nullptr;       // hipcub's temporary storage
+    size_t tmp_bytes = 0;
+    void* ev = nullptr;          // hipEvent_t after the latest use (null: never used)
+    void* last_stream = nullptr;
+    int64_t last_n = -1;         // rays of the last RT_RAYS_REORDER call (-1: none yet)
+    bool last_sorted = false;    // false: that call was one packet (n <= 64), traced in the given order
+  } rays;
+  float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
+  bool ray_bounds_valid = false;
   bool pending = false;
 };
 
@@ -264,4 +279,7 @@ int resolve_devices(rt_scene_opts& o);
 int device_replicate(rt_scene* s);
 int current_device();  // -1 without a GPU
 void device_release(rt_scene* s);
+void ray_stream_release(rt_scene* s);  // rt_rays.hip; the scene's device is current
+// world bounds of the scene's vertices, computed at first use (rt_host.cpp)
+const float* scene_ray_bounds(rt_scene* s);
 }  // namespace rt

@@ -20,6 +20,12 @@ RT_FRAME_STATS = 2
 RT_FRAME_TIMELINE = 4
 RT_FRAME_WAVE_STATS = 8
 RT_DEVICE_NONE = -2
+# ray streams (rt_trace_stream)
+RT_RAYS_CLOSEST = 0
+RT_RAYS_SHADOW = 1
+RT_RAYS_COLOR = 2
+RT_RAYS_REORDER = 1
+RT_RAYS_STATS = 2
 
 # Every symbol include/rt/rt_api.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -35,6 +41,7 @@ EXPORTS = [
     "rt_debug_timeline", "rt_debug_counters", "rt_box_colors_random", "rt_scene_set_box_colors", "rt_frame_shard_tiles",
     "rt_debug_record_layout", "rt_debug_scene_flags", "rt_debug_env_knobs", "rt_debug_tree_cost",
     "rt_synchronize_devices", "rt_debug_lpt_stats", "rt_debug_wave_stats", "rt_debug_frame_plan",
+    "rt_trace_stream", "rt_rays_camera", "rt_scene_ray_bounds", "rt_debug_ray_keys", "rt_debug_ray_order",
 ]
 RT_MAX_DEVICES = 16
 RT_DEVICES_ALL = -1
@@ -88,6 +95,11 @@ RT_LIGHT_POINT, RT_LIGHT_DIRECTIONAL = 0, 1
 
 class RandState(C.Structure):
     _fields_ = [("r", C.c_uint32 * 34), ("k", C.c_uint32)]
+
+
+class RayStream(C.Structure):
+    _fields_ = [("n", C.c_int32), ("a3", C.c_void_p), ("b3", C.c_void_p), ("face", C.c_void_p), ("t", C.c_void_p),
+                ("P3", C.c_void_p), ("N3", C.c_void_p), ("blocked", C.c_void_p), ("rgb3", C.c_void_p)]
 
 
 class Frame(C.Structure):
@@ -186,6 +198,13 @@ def lib():
         L.rt_frame_shard_tiles.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32]
         L.rt_frame_shard_tiles.restype = C.c_int32
         L.rt_scene_set_box_colors.argtypes = [vp, vp]
+        # ray streams (builds from before them, loaded for A/B through RTAMD_LIB, lack these)
+        if hasattr(L, "rt_trace_stream"):
+            L.rt_trace_stream.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(RayStream), vp, C.c_int32, vp]
+            L.rt_rays_camera.argtypes = [vp, C.POINTER(Camera), C.c_int32, C.c_int32, vp, vp, vp]
+            L.rt_scene_ray_bounds.argtypes = [vp, vp]
+            L.rt_debug_ray_keys.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp]
+            L.rt_debug_ray_order.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -551,10 +570,129 @@ class Scene:
         check(lib().rt_trace_shadow(self.h, len(P), _p(P), _p(L), _p(out)))
         return out
 
+    # ---- ray streams: device-resident ray lists (torch tensors, or anything with data_ptr()) ----
+    _STREAM_OUTPUTS = {
+        RT_RAYS_CLOSEST: (("face", "int32", 1, True), ("t", "float32", 1, True), ("P", "float32", 3, False),
+                          ("N", "float32", 3, False)),
+        RT_RAYS_SHADOW: (("blocked", "int32", 1, True),),
+        RT_RAYS_COLOR: (("rgb", "float32", 3, True), ("face", "int32", 1, False), ("t", "float32", 1, False)),
+    }
+
+    def trace_stream(self, query, a, b, *, lights=None, reorder=False, stats=False, stream=None, out=None):
+        """rt_trace_stream on device tensors: a, b float32 [n,3] (origins and directions; P and L for
+        RT_RAYS_SHADOW). Returns a dict of device tensors: CLOSEST face, t, P, N; SHADOW blocked; COLOR rgb,
+        face, t. out: a dict of preallocated outputs (then only the query's required outputs and the ones
+        given are written); missing outputs are allocated with torch beside a. stream: a raw hipStream_t
+        (torch.cuda.current_stream().cuda_stream) or an object with .cuda_stream -- the call is enqueued there
+        and returns at once; None = the scene's own stream, synchronous. reorder: RT_RAYS_REORDER (same
+        bits, coherence order); stats: RT_RAYS_STATS (then read Scene.counters())."""
+        if query not in self._STREAM_OUTPUTS:
+            raise ValueError(f"trace_stream: bad query {query}")
+        n = _device_rays(a, "a")
+        if _device_rays(b, "b") != n:
+            raise ValueError("trace_stream: a and b differ in length")
+        given = dict(out or {})
+        res = {}
+        for name, dtype, width, required in self._STREAM_OUTPUTS[query]:
+            x = given.pop(name, None)
+            if x is None and (required or out is None):
+                x = _torch_empty(a, (n, 3) if width == 3 else (n,), dtype)
+            if x is not None:
+                _check_device_array(x, dtype, (n, 3) if width == 3 else (n,), name)
+                res[name] = x
+        if given:
+            raise ValueError(f"trace_stream: outputs {sorted(given)} do not belong to query {query}")
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        rs = RayStream(n, a.data_ptr(), b.data_ptr(), ptr("face"), ptr("t"), ptr("P"), ptr("N"), ptr("blocked"), ptr("rgb"))
+        lights = lights if lights is not None else []
+        L = self._lights(lights)
+        flags = (RT_RAYS_REORDER if reorder else 0) | (RT_RAYS_STATS if stats else 0)
+        check(lib().rt_trace_stream(self.h, query, flags, C.byref(rs), C.cast(L, C.c_void_p), len(lights), _stream_ptr(stream)))
+        return res
+
+    def camera_rays(self, cam, W, H, stream=None, out=None):
+        """rt_rays_camera: the frame's primary rays as device tensors (origins [W*H,3], directions [W*H,3]),
+        pixel (px, py) at index py * W + px. out: (origins, dirs) to fill; else allocated with torch on the
+        scene's device."""
+        if out is None:
+            import torch
+            dev = torch.device("cuda", self.info()["device"])
+            out = (torch.empty((W * H, 3), dtype=torch.float32, device=dev), torch.empty((W * H, 3), dtype=torch.float32, device=dev))
+        o, d = out
+        _check_device_array(o, "float32", (W * H, 3), "origins")
+        _check_device_array(d, "float32", (W * H, 3), "dirs")
+        check(lib().rt_rays_camera(self.h, C.byref(cam), W, H, o.data_ptr(), d.data_ptr(), _stream_ptr(stream)))
+        return o, d
+
+    def ray_bounds(self):
+        """The grid of the coherence keys: world bounds of the scene's vertices, float32 [6] (lo xyz, hi xyz)."""
+        b = np.zeros(6, np.float32)
+        check(lib().rt_scene_ray_bounds(self.h, _p(b)))
+        return b
+
+    def ray_order(self):
+        """The order of the last reorder=True call (rt_debug_ray_order): uint32 [n], entry k = the ray traced k-th."""
+        n = C.c_int64(0)
+        check(lib().rt_debug_ray_order(self.h, 0, None, C.byref(n)))
+        out = np.zeros(n.value, np.uint32)
+        check(lib().rt_debug_ray_order(self.h, n.value, _p(out), C.byref(n)))
+        return out
+
     def __del__(self):
         if getattr(self, "h", None) and _lib is not None:
             _lib.rt_scene_destroy(self.h)
             self.h = None
+
+
+def _dtype_name(x):
+    return str(x.dtype).replace("torch.", "")
+
+
+def _check_device_array(x, dtype, shape, name):
+    """dtype, shape and contiguity of a device tensor handed to the library (checked before the call)."""
+    if not hasattr(x, "data_ptr"):
+        raise TypeError(f"{name}: expected a device tensor with data_ptr(), got {type(x).__name__}")
+    if _dtype_name(x) != dtype:
+        raise TypeError(f"{name}: dtype {_dtype_name(x)}, expected {dtype}")
+    if tuple(x.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(x.shape)}, expected {tuple(shape)}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+
+
+def _device_rays(x, name):
+    if not hasattr(x, "data_ptr"):
+        raise TypeError(f"{name}: expected a device tensor with data_ptr(), got {type(x).__name__}")
+    if len(x.shape) != 2 or x.shape[1] != 3:
+        raise ValueError(f"{name}: shape {tuple(x.shape)}, expected [n, 3]")
+    _check_device_array(x, "float32", (x.shape[0], 3), name)
+    return int(x.shape[0])
+
+
+def _torch_empty(like, shape, dtype):
+    try:
+        import torch
+    except ImportError as e:  # torch is only needed to allocate outputs the caller did not pass
+        raise RTError("trace_stream: pass every output in out= when torch is not importable") from e
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=like.device)
+
+
+def _stream_ptr(stream):
+    if stream is None:
+        return None
+    return C.c_void_p(int(getattr(stream, "cuda_stream", stream)))
+
+
+def ray_keys(query, a, b, bounds6):
+    """rt_debug_ray_keys: the coherence keys of host rays a, b [n,3] on the grid bounds6 -> uint32 [n]."""
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, 3)
+    b = np.ascontiguousarray(b, np.float32).reshape(-1, 3)
+    if len(a) != len(b):
+        raise ValueError("ray_keys: a and b differ in length")
+    b6 = np.ascontiguousarray(bounds6, np.float32).reshape(6)
+    out = np.zeros(len(a), np.uint32)
+    check(lib().rt_debug_ray_keys(query, len(a), _p(a), _p(b), _p(b6), _p(out)))
+    return out
 
 
 def record_layout(n_nodes, n_tris, n_wide):
