@@ -23,38 +23,26 @@ $(shell mkdir -p $(OBJ) && echo '#define RT_SOURCE_HASH "$(SRC_HASH)"' > $(VERSI
 
 all: $(LIB) variants oracle cli
 
-$(OBJ)/rt_device.o: $(PKG)/csrc/rt_device.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# one object per source: every csrc/*.cpp is host code of the library (rt_version.cpp has its own rule: it
+# includes the generated hash), every csrc/*.hip but the A/B variants is device code of it
+HOST_OBJS := $(patsubst $(PKG)/csrc/%.cpp,$(OBJ)/%.o,$(filter-out %/rt_version.cpp,$(sort $(wildcard $(PKG)/csrc/*.cpp))))
+DEV_OBJS  := $(patsubst $(PKG)/csrc/%.hip,$(OBJ)/%.o,$(filter-out %/rt_variants.hip,$(sort $(wildcard $(PKG)/csrc/*.hip))))
+PRODUCT_OBJS := $(DEV_OBJS) $(HOST_OBJS) $(OBJ)/rt_version.o
 
-$(OBJ)/rt_host.o: $(PKG)/csrc/rt_host.cpp $(HDRS)
+$(OBJ)/%.o: $(PKG)/csrc/%.hip $(HDRS)
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA_HIPFLAGS) -c $< -o $@
+
+$(OBJ)/%.o: $(PKG)/csrc/%.cpp $(HDRS)
 	@mkdir -p $(OBJ)
 	$(CXX) $(CXXFLAGS) -c $< -o $@
 
-$(OBJ)/rt_variants.o: $(PKG)/csrc/rt_variants.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-$(OBJ)/rt_rays.o: $(PKG)/csrc/rt_rays.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c $< -o $@
-
-$(OBJ)/rt_build.o: $(PKG)/csrc/rt_build.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -Wno-unused-result -c $< -o $@
-
-$(OBJ)/rt_boxes.o: $(PKG)/csrc/rt_boxes.hip $(HDRS)
-	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+# hipcub's and the build kernels' ignored [[nodiscard]] results
+$(OBJ)/rt_rays.o $(OBJ)/rt_build.o: EXTRA_HIPFLAGS := -Wno-unused-result
 
 $(OBJ)/rt_version.o: $(PKG)/csrc/rt_version.cpp $(VERSION_H) include/rt/rt_api.h
 	$(CXX) $(CXXFLAGS) -I$(OBJ) -c $< -o $@
 
-$(OBJ)/rt_cache.o: $(PKG)/csrc/rt_cache.cpp $(HDRS)
-	@mkdir -p $(OBJ)
-	$(CXX) $(CXXFLAGS) -c $< -o $@
-
-PRODUCT_OBJS := $(OBJ)/rt_device.o $(OBJ)/rt_rays.o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
 $(LIB): $(PRODUCT_OBJS)
 	@mkdir -p $(PKG)/lib
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $^ -lpthread
@@ -69,12 +57,13 @@ $(VARLIB): $(PRODUCT_OBJS) $(OBJ)/rt_variants.o
 
 # A/B builds of the same sources with extra device flags (experiments only):
 #   make ablib TAG=noslp EXTRA="-fno-slp-vectorize"  ->  lib/librtamd_noslp.so  (select with RTAMD_LIB)
-ablib: $(PKG)/csrc/rt_device.hip $(PKG)/csrc/rt_rays.hip $(HDRS) $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o
+AB_SHARED := $(filter-out $(OBJ)/rt_device.o $(OBJ)/rt_rays.o,$(PRODUCT_OBJS))
+ablib: $(PKG)/csrc/rt_device.hip $(PKG)/csrc/rt_rays.hip $(HDRS) $(AB_SHARED)
 	@mkdir -p $(OBJ) $(PKG)/lib
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $< -o $(OBJ)/rt_device_$(TAG).o
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -Wno-unused-result -c $(PKG)/csrc/rt_rays.hip -o $(OBJ)/rt_rays_$(TAG).o
 	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $(PKG)/csrc/rt_variants.hip -o $(OBJ)/rt_variants_$(TAG).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(OBJ)/rt_device_$(TAG).o $(OBJ)/rt_rays_$(TAG).o $(OBJ)/rt_variants_$(TAG).o $(OBJ)/rt_host.o $(OBJ)/rt_cache.o $(OBJ)/rt_build.o $(OBJ)/rt_boxes.o $(OBJ)/rt_version.o -lpthread
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(OBJ)/rt_device_$(TAG).o $(OBJ)/rt_rays_$(TAG).o $(OBJ)/rt_variants_$(TAG).o $(AB_SHARED) -lpthread
 
 # debug build of the same sources with every scalar prefetch offset checked on the device (RT_CHECK_PREFETCH:
 # an out-of-range offset is recorded and fails the next rt_synchronize) -> lib/librtamd_pfcheck.so,

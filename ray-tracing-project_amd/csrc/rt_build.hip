@@ -11,7 +11,7 @@
 // compacted in order -- until one cluster is left. Agglomerative clustering by surface area gives trees of
 // SAH quality at GPU speed. A bottom-up SAH pass (same costs as the host builders: triangle 1, node step
 // 0.7) then marks the subtrees of <= leaf_size triangles that are cheaper as one leaf; the host lays the
-// tree out depth first (rt_host.cpp build_bvh_ploc). Child boxes get the same conservative padding as the
+// tree out depth first (rt_layout.cpp build_bvh_ploc). Child boxes get the same conservative padding as the
 // host builders either way, so traversal stays exact.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -373,7 +373,7 @@ int gpu_build_lbvh(int device, const std::vector<TriRec64>& face_recs, const flo
 
 // PLOC (see the top of the file). face_recs: one TriRec64 per face. Outputs the n - 1 interior nodes
 // (root n - 2): children (>= 0 interior node, < 0 ~face), boxes, the SAH collapse flag per node; the
-// host lays the tree out (rt_host.cpp build_bvh_ploc). RT_ERR_INVALID when the clustering cannot finish
+// host lays the tree out (rt_layout.cpp build_bvh_ploc). RT_ERR_INVALID when the clustering cannot finish
 // (an iteration without a merge: non-finite boxes), so the caller builds on the host instead.
 int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const float lo[3], const float hi[3],
                    int leaf_size, int radius, float k_trav, std::vector<int32_t>& child2, std::vector<float>& box6,
@@ -564,7 +564,7 @@ __device__ __forceinline__ int sp_bin(const Box6& b, int k, float x) {
 __device__ __forceinline__ float fdown(double x) { const float f = (float)x; return (double)f > x ? nextafterf(f, -INFINITY) : f; }
 __device__ __forceinline__ float fup(double x) { const float f = (float)x; return (double)f < x ? nextafterf(f, INFINITY) : f; }
 // bounds of triangle `t` (its record's vertices: the culling bounds) inside [a, b] on axis k, intersected
-// with `within` (the reference's box); false if empty -- the host SBVH's clip (rt_host.cpp SbvhBuilder)
+// with `within` (the reference's box); false if empty -- the host SBVH's clip (rt_builders.cpp SbvhBuilder)
 __device__ bool clip_tri(const TriRec64& t, int k, float a, float b, const Box6& within, Box6& out) {
   const double v[3][3] = {{t.w0x, t.w0y, t.w0z}, {t.w1x, t.w1y, t.w1z}, {t.w2x, t.w2y, t.w2z}};
   double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};

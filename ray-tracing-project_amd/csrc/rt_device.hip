@@ -613,7 +613,7 @@ int device_upload(rt_scene* s) {
       parallel_for(nn, [&](size_t b, size_t e) {
         for (size_t i = b; i < e; i++) {
           Node64 nd = hs.nodes[i];
-          const uint32_t order = nd.pad0;  // octant_order() (rt_host.cpp), moved into the low offset bits
+          const uint32_t order = nd.pad0;  // octant_order() (rt_layout.cpp), moved into the low offset bits
           nd.pad0 = pf(nd.child0) | (order & 0x3Fu);
           nd.pad1 = pf(nd.child1) | ((order >> 6) & 0x3u);
           if (!is_leaf(nd.child0)) nd.child0 *= 64u;

@@ -36,9 +36,9 @@ constexpr int kMaxLeaf = 16;
 constexpr uint32_t kMaxFaces = (1u << 25) - 1;
 constexpr int kMaxDepth = 60;  // wave stack holds 64 entries; occupancy <= depth
 // TriRec64::box bit 31: the triangle's interpolated normal can never be the zero vector (see
-// rt_host.cpp safe_normal()), so calculateDistance's norm()==0 rejection never fires for it
+// rt_layout.cpp safe_normal()), so calculateDistance's norm()==0 rejection never fires for it
 constexpr uint32_t kSafeNormalBit = 0x80000000u;
-// TriRec64::box bit 30: reference-box certificate (rt_host.cpp box_certified()): for a ray whose
+// TriRec64::box bit 30: reference-box certificate (rt_layout.cpp box_certified()): for a ray whose
 // object-space origin lies within DevScene::cert_origin_max (max norm), every hit point the reference's
 // edge tests accept on this face lies inside the face's reference box by more than the box fast path's
 // margin, so intersectBox accepts and the accept path skips the box predicate

@@ -185,7 +185,7 @@ __device__ __forceinline__ float nudge(float x) { return fabsf(x) < 1e-20f ? cop
 
 // Culling set-up of a ray, once per ray.
 // The BVH boxes carry a static pad for the scene-scale rounding of the reference's arithmetic (bvh_pad,
-// rt_host.cpp). The rounding of the reference's hit point P = o + t d, and of this slab test, also grows
+// rt_layout.cpp). The rounding of the reference's hit point P = o + t d, and of this slab test, also grows
 // with the ray origin's magnitude: both are a few ulp of |o| + |t d| <= 2|o| + R per axis (R: the scene's
 // magnitude). So every ray grows the boxes it tests by its own pad p = kCullPadRel * |o|_inf, folded into
 // two per-axis offsets: with box [lo - p, hi + p] the plane distances are fma(lo, 1/d, -(o + p)/d) and
@@ -415,7 +415,7 @@ __device__ __forceinline__ void test_tri(const DevScene& P, const TriRec64& tr, 
 // production closest-hit / any-hit path is traverse_fast() below (same visit order, leaner per-node
 // code); this loop serves the counting run and the VGPR-stack A/B variant (rt_variants.hip). Octant-
 // specialised loops take the near child from the node's precomputed order bit for the wave's octant
-// (split-axis rule, octant_order() in rt_host.cpp) instead of a lane-majority vote: 3 fewer SALU and one
+// (split-axis rule, octant_order() in rt_layout.cpp) instead of a lane-majority vote: 3 fewer SALU and one
 // fewer v_cmp per node step (C3 +3.7% at 4 frames in flight, bunny +2.6%).
 // Node64::pad0 / pad1 hold the children's record offsets (multiples of 64, the prefetch targets), so the
 // eight octant order bits travel in their low bits: octants 0-5 in pad0 bits 0-5, octants 6-7 in pad1

@@ -67,23 +67,16 @@ struct HostScene {
   int32_t depth = 0, leaves = 0, depth4 = 0;
 };
 
-void build_ref_boxes(HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes);
-// the same partition on the GPU (rt_boxes.hip); *nonfinite: some vertex coordinate is not finite and
-// nothing was built (the caller uses the host builder)
+// the reference-box partition on the GPU (rt_boxes.hip; on the host: rt_refboxes.cpp); *nonfinite: some
+// vertex coordinate is not finite and nothing was built (the caller uses the host builder)
 int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes,
                         double* gpu_ms, bool* nonfinite);
-// face_rank / face_box from hs.boxes (boxes in creation order, faces in in-box order)
-void assign_box_ranks(HostScene& hs);
-void build_bvh(HostScene& hs, int leaf_size, bool spatial);  // spatial: SBVH (RT_BUILDER_SBVH)
-bool build_bvh_gpu(HostScene& hs, int device, int leaf_size, double* gpu_ms);
-bool build_bvh_ploc(HostScene& hs, int device, int leaf_size, double* gpu_ms);
 int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const float lo[3], const float hi[3],
                    int leaf_size, int radius, float k_trav, std::vector<int32_t>& child2, std::vector<float>& box6,
                    std::vector<uint8_t>& leaf, double* gpu_ms, int* iterations, int rule);
 int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const float lo[3], const float hi[3],
                   int leaf_size, float k_trav, bool spatial, float budget, float alpha, std::vector<uint32_t>& nchild,
                   std::vector<float>& ncb, std::vector<uint32_t>& slot_face, double* gpu_ms, int* levels);
-bool build_bvh_sah_gpu(HostScene& hs, int device, int leaf_size, bool spatial, double* gpu_ms);
 int gpu_build_lbvh(int device, const std::vector<TriRec64>& face_recs, const float lo[3], const float hi[3],
                    int leaf_size, float pad, std::vector<Node64>& nodes, std::vector<TriRec64>& tris, double* gpu_ms);
 // [0, n) in contiguous chunks on up to 16 host threads: f(begin, end) (rt_host.cpp)
@@ -95,9 +88,8 @@ void device_warmup(int device);
 // host <-> device copies of large pageable buffers through pinned staging (rt_device.hip)
 int h2d(void* dst, const void* src, size_t bytes);
 int d2h(void* dst, const void* src, size_t bytes);
-void build_bvh4(HostScene& hs);
+// rt_layout.cpp (the declarations only the host sources use are in rt_host.h)
 void build_wide(HostScene& hs);
-float bvh_pad(const float lo[3], const float hi[3]);
 // fills hs.av (see HostScene::av) from wv / fnn / fdist; leaves it empty when no face needs it
 void accept_region(HostScene& hs);
 // vertex j of the triangle the culling boxes must bound for face f

@@ -1,6 +1,6 @@
 """Adversarial probes of the reference-box certificates.
 
-A face carrying the certificate (TriRec64.box bit 30, `box_certified` in rt_host.cpp) lets the accept
+A face carrying the certificate (TriRec64.box bit 30, `box_certified` in rt_layout.cpp) lets the accept
 path skip the reference's own box predicate (`intersectBox`, src/flyscene.cpp:484-507, as called from
 calculateMinimumFace :381-391 and shadow :510-526) for every ray whose object-space origin o2 has
 |o2|_inf <= Ro (the certified range). The argument is analytic; these tests aim

@@ -546,7 +546,7 @@ def test_box_certificates_need_a_similarity_and_matching_normals(rt, orc):
 def test_tilted_normals_trees_bound_the_accept_region(rt, orc, model):
     """Under a rotating or non-uniformly scaling model matrix the reference tests world edges against the
     object-space face normal n (flyscene.cpp:444-478, 573-590), so the hit points it accepts lie on the world
-    triangle projected along n onto n's plane (rt_host.cpp accept_region), up to a few % of a triangle's
+    triangle projected along n onto n's plane (rt_layout.cpp accept_region), up to a few % of a triangle's
     size away from the world triangle. The oracle's hits must lie in that projection's box (the theory), a
     good share of them outside the world triangle's box (why the builders must bound the projection), and
     every tree must hold the projections (the validator, which checks bound_vert boxes)."""
@@ -709,14 +709,16 @@ def test_builder_selected_through_abi(rt, tmp_path):
         assert rt.Scene.load(p, device=rt.RT_DEVICE_NONE).info()["builder"] == b
 
 
-def test_sbvh_build_is_deterministic(rt, tmp_path):
+@pytest.mark.parametrize("builder", ["RT_BUILDER_SBVH", "RT_BUILDER_SAH"])
+def test_sbvh_build_is_deterministic(rt, tmp_path, builder):
     """the spatial-split builder's reference budget is shared out per subtree, so the tree does
-    not depend on the order its parallel subtree tasks run in: two builds save byte-identical caches."""
+    not depend on the order its parallel subtree tasks run in: two builds save byte-identical caches. The
+    binned SAH builder likewise (its chunked bins and bounds merge in chunk order)."""
     mesh = _soup(rt, 200_000)
     paths = []
     for k in range(2):
-        sc = rt.Scene(mesh, device=rt.RT_DEVICE_NONE)
-        assert sc.info()["builder"] == rt.RT_BUILDER_SBVH
+        sc = rt.Scene(mesh, device=rt.RT_DEVICE_NONE, builder=getattr(rt, builder))
+        assert sc.info()["builder"] == getattr(rt, builder)
         p = tmp_path / f"s{k}.rtscene"
         sc.save(p)
         paths.append(p)

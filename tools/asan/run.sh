@@ -10,11 +10,16 @@ mkdir -p $OUT
 HIPCC=/opt/rocm/bin/hipcc
 SAN="-fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined"
 FLAGS="-O1 -g -std=c++17 -ffp-contract=off -Iinclude -Iray-tracing-project_amd/csrc"
-for f in rt_host rt_cache; do
-  $HIPCC $FLAGS $SAN -fno-gpu-sanitize -c ray-tracing-project_amd/csrc/$f.cpp -o $OUT/$f.o
+CSRC=ray-tracing-project_amd/csrc
+OBJS=
+for src in $CSRC/*.cpp; do  # every host source the Makefile links (rt_version.cpp only embeds the source hash)
+  f=$(basename $src .cpp)
+  [ $f = rt_version ] && continue
+  $HIPCC $FLAGS $SAN -fno-gpu-sanitize -c $src -o $OUT/$f.o
+  OBJS="$OBJS $OUT/$f.o"
 done
 $HIPCC $FLAGS $SAN -fno-gpu-sanitize -c tools/asan/host_asan.cpp -o $OUT/host_asan.o
-$HIPCC $SAN -fno-gpu-sanitize --offload-arch=gfx950 -o $OUT/host_asan $OUT/host_asan.o $OUT/rt_host.o $OUT/rt_cache.o \
+$HIPCC $SAN -fno-gpu-sanitize --offload-arch=gfx950 -o $OUT/host_asan $OUT/host_asan.o $OBJS \
     ray-tracing-project_amd/build/rt_device.o ray-tracing-project_amd/build/rt_rays.o ray-tracing-project_amd/build/rt_build.o \
     ray-tracing-project_amd/build/rt_boxes.o -lpthread
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $OUT/host_asan scenes
