@@ -444,6 +444,52 @@ int rt_debug_ray_keys(int32_t query, int32_t n, const float* a3, const float* b3
  * Waits for that call. */
 int rt_debug_ray_order(rt_scene* s, int64_t capacity, uint32_t* perm_out, int64_t* n_out); /* last REORDER call */
 
+/* ---------------------------------------------------------------------------------------------
+ * traceRay for a device ray list at any recursion limit and in either mode: what rt_frame.mode / max_depth
+ * are to frames (feature test: RT_HAS_RAY_DEPTH; the API version stays 4).
+ *
+ * rt_trace_stream_color(s, flags, rays, lights, n_lights, mode, max_depth, hip_stream)
+ *   rays        a3 origins, b3 directions; rgb3 required, face and t optional (the first hit; a miss: -1, +inf).
+ *               The other members are ignored.
+ *   mode        RT_MODE_PRIMARY: no shadow rays; RT_MODE_FULL: a shadow ray per light per hit. Anything else:
+ *               RT_ERR_INVALID ("bad mode").
+ *   max_depth   0 = the mode's own limit (PRIMARY 1, FULL 2); 1..RT_MAX_TRACE_DEPTH; else RT_ERR_INVALID.
+ *   Ray i's colour, face and t are exactly what rt_render writes for a pixel whose camera ray is ray i, in that
+ *   mode at that depth: a primary miss gives the scene's background, the material state stays with the chain
+ *   from level to level and the final ks folds the levels, as in the frame kernel (csrc/rt_kernels.h
+ *   k_render_depth; the list kernel k_rays_depth runs a copy of its level loop).
+ *   flags       RT_RAYS_REORDER, RT_RAYS_STATS as rt_trace_stream (the reorder groups level 0's rays).
+ *               RT_RAYS_WAVEFRONT: trace level by level instead of chain by chain. Every level is a closest-hit
+ *               stage over the rays still alive, a regroup of the hits, a shade stage over them (its shadow
+ *               packets are then made of neighbouring hit points; PRIMARY mode and calls without lights have no
+ *               shadow rays and shade inside the closest stage), and a regroup of the reflection rays for the
+ *               next level; a last pass folds the levels and writes each ray's outputs at its own index. Without
+ *               RT_RAYS_REORDER a regroup is a stable compaction (survivors keep list order), with it a stable
+ *               sort by the coherence key of the stage's own rays (closest: origin and direction; shade: hit
+ *               point and direction to the first light). Every output bit equals the flagless call's. No count
+ *               is read back: each stage is launched for n and its packets leave early. Scratch: 124 + 12 D
+ *               bytes per ray at depth D (172 B at 4, 316 B at 16; csrc/rt_wavefront.h) plus the sorts'
+ *               temporary storage, scene-owned, grown geometrically and ordered across streams as the reorder
+ *               scratch is; a failed allocation returns RT_ERR_NOMEM. Opt-in: README.md has what was measured.
+ *               RT_RAYS_STATS with it: slots 4 (rays), 5 (primary hits), 6 (all rays) equal the in-order
+ *               call's; slots 0..3 depend on the grouping.
+ *   FULL at depth 0 or 2 without RT_RAYS_WAVEFRONT is rt_trace_stream(RT_RAYS_COLOR), same kernel. Every other
+ *   combination runs binary-tree kernels only and returns RT_ERR_UNSUPPORTED under the 4-wide A/B variant.
+ *   Checks, n == 0, host-only scenes and stream semantics: as rt_trace_stream. rt_trace_stream itself keeps
+ *   refusing flag 4.
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_RAY_DEPTH 1
+#define RT_RAYS_WAVEFRONT 4   /* rt_trace_stream_color only */
+int rt_trace_stream_color(rt_scene* s, int32_t flags, const rt_ray_stream* rays,
+                          const rt_light* lights, int32_t n_lights,
+                          int32_t mode, int32_t max_depth, void* hip_stream);
+/* The levels of the scene's last RT_RAYS_WAVEFRONT call (waits for it): *n_levels = its depth D; for d < D,
+ * out2[2 d] = rays that entered level d's closest-hit stage, out2[2 d + 1] = how many of them hit. capacity
+ * (levels) smaller than D, or no such call yet: RT_ERR_INVALID. out2 NULL: only *n_levels. */
+int rt_debug_ray_levels(rt_scene* s, int32_t capacity, int64_t* out2, int32_t* n_levels);
+/* After an RT_RAYS_WAVEFRONT | RT_RAYS_REORDER call rt_debug_ray_order returns level 0's order, the permutation
+ * the plain RT_RAYS_REORDER call computes for that list; a wavefront call without the reorder leaves it alone. */
+
 /* createDebugRay (flyscene.cpp:129-173) without the GL cylinders: the camera ray through a
  * (float) mouse position and its reflection chain, up to max_depth segments; every segment carries the
  * first ray's traceRay colour; a miss ends the chain with a 10-unit segment. *n_out = segments written. */

@@ -1843,6 +1843,101 @@ void k_rays_color(FrameParams P, RayParams R) {
   if (R.t) R.t[i] = h.t;
 }
 
+// k_render_depth's level loop for the list kernel below: cur is level 0's ray, the return value traceRay's colour,
+// h0 / face0 the first hit (face0 = ~0: a miss). A copy, statement for statement, and not a function both kernels
+// share: with the loop moved into a function k_render_depth's scratch size and spill counts changed (make asm), and
+// the frame kernels stay as they are. Keep the two in step.
+template <bool STATS>
+__device__ __forceinline__ f3 trace_depth(const FrameParams& P, Ray cur, bool active, WaveLds<TRAV_B2_LDS, STATS>& lds,
+                                          int slot, uint32_t* cnt, Hit& h0, uint32_t& face0) {
+  MatState st = load_mat(P.defmat);
+  f3 direct[RT_MAX_TRACE_DEPTH];
+  int levels = 0;  // levels whose closest hit exists (the chain stops at the first miss)
+  bool act = active;
+  h0 = Hit{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  face0 = 0xFFFFFFFFu;
+  const int D = P.max_depth;
+#pragma clang loop unroll(disable)
+  for (int d = 0; d < D; d++) {
+    Hit h{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    bool dummy = false;
+    if (d == 0) trace_oct<false, STATS, TRAV_B2_LDS>(P.sc, cur, act, h, dummy, lds, slot, cnt);
+    else trace<false, STATS, TRAV_B2_LDS>(P.sc, cur, act, h, dummy, lds, slot, cnt);
+    const bool hit = act && h.t != INFINITY;
+    if (STATS && d == 0 && hit) cnt[ST_HITS]++;
+    HitInfo hi;
+    hi.mat = -1;
+    hi.face = 0xFFFFFFFFu;
+    hi.p = f3{0.0f, 0.0f, 0.0f};
+    hi.n = f3{0.0f, 0.0f, 0.0f};
+    if (hit) {
+      const TriRec64 tr = vload_tri(P.sc.tris, h.slot);
+      hi.face = tr.face;
+      hi.p = f3{cur.o.x + h.t * cur.d.x, cur.o.y + h.t * cur.d.y, cur.o.z + h.t * cur.d.z};
+      hi.n = hit_normal(P.sc, tr, h.slot, hi.p, hi.mat);
+    }
+    if (d == 0) {
+      h0 = h;
+      face0 = hit ? hi.face : 0xFFFFFFFFu;
+    }
+    const f3 dc = P.shadows ? calc_color<true, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, slot, cnt)
+                            : calc_color<false, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, slot, cnt);
+    if (hit) {
+      direct[d] = dc;
+      levels = d + 1;
+      if (hi.mat != -1) st.ks = load_mat(P.sc.mats[hi.mat]).ks;  // traceRay :355-358
+    }
+    if (d + 1 == D) break;  // traceRay(depth + 1) returns black without tracing (:318-320)
+    // reflect(dir.normalized(), interpolateNormal(...)), offset 0.001 (flyscene.cpp:361-363)
+    Ray rr;
+    rr.d = reflect(normalized(cur.d), hi.n);
+    rr.o = offset(hi.p, rr.d, 0.001f);
+    rr.o2 = affv3(P.Minv, rr.o);
+    setup_cull(rr, P.sc.static_pad);
+    if (STATS && hit) cnt[ST_TOTAL]++;
+    cur = rr;
+    act = hit;
+    if (ballot(act) == 0) break;  // no lane of the wave continues
+  }
+  f3 col{0.0f, 0.0f, 0.0f};
+  for (int d = levels - 1; d >= 0; d--)
+    col = f3{clamp01(direct[d].x + col.x * st.ks.x), clamp01(direct[d].y + col.y * st.ks.y),
+             clamp01(direct[d].z + col.z * st.ks.z)};
+  if (D > 0 && levels == 0) col = f3{P.bg[0], P.bg[1], P.bg[2]};  // primary miss: BACKGROUND_COLOR (:327-332)
+  return col;
+}
+
+// traceRay(o, d, 0) at any recursion limit, with or without shadow rays (P.max_depth, P.shadows), for a list of
+// rays (rt_trace_stream_color): the level loop (trace_depth) under the list packets' addressing
+template <bool STATS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEu)))
+void k_rays_depth(FrameParams P, RayParams R) {
+  __shared__ WaveLds<TRAV_B2_LDS, STATS> lds;
+  const int lane = threadIdx.x & 63, wv = (int)uniform(threadIdx.x >> 6);
+  const int base = (int)uniform((blockIdx.x * 4 + (threadIdx.x >> 6)) * 64);
+  if (base >= R.n) return;
+  const bool active = base + lane < R.n;
+  const int i = ray_index(R, active ? base + lane : base);
+  uint32_t cnt_[STATS ? ST_COUNT : 1] = {};
+  uint32_t* const cnt = STATS ? cnt_ : nullptr;
+  Ray r;
+  r.o = ld3(R.o + 3 * (size_t)i);
+  r.d = ld3(R.d + 3 * (size_t)i);
+  r.o2 = affv3(P.Minv, r.o);
+  setup_cull(r, P.sc.static_pad);
+  if (STATS && active) { cnt[ST_RAYS]++; cnt[ST_TOTAL]++; }
+  Hit h;
+  uint32_t face0;
+  const f3 col = trace_depth<STATS>(P, r, active, lds, wv, cnt, h, face0);
+  if (STATS) flush_stats(P, cnt, lane);
+  if (!active) return;
+  R.rgb[3 * (size_t)i + 0] = col.x;
+  R.rgb[3 * (size_t)i + 1] = col.y;
+  R.rgb[3 * (size_t)i + 2] = col.z;
+  if (R.face) R.face[i] = face0 != 0xFFFFFFFFu ? (int32_t)face0 : -1;
+  if (R.t) R.t[i] = h.t;
+}
+
 // ------------------------------------------------------------------------------------------------
 // The A/B kernel variants (RT_KERNEL_VARIANT bits, rt_debug_set_variant) live in rt_variants.hip and are
 // linked only into the variants library (`make variants` -> lib/librtamd_variants.so): the product

@@ -1,7 +1,8 @@
 // rt_rays.hip -- ray-list queries of the MI355X ray-traversal library: the device-resident, stream-ordered
 // path (rt_trace_stream, rt_rays_camera), its coherence reorder (key kernel + radix sort + indexed packets),
 // and the host-pointer entry points (rt_trace_closest and its siblings), which are "upload, stream path,
-// download". The packet kernels themselves are rt_kernels.h k_rays / k_rays_color.
+// download". The packet kernels themselves are rt_kernels.h k_rays / k_rays_color / k_rays_depth; the stage kernels
+// of RT_RAYS_WAVEFRONT are rt_wavefront.h, their host glue (enqueue_wavefront) is here.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -11,6 +12,7 @@
 #include "rt_dispatch.h"
 #include "rt_kernels.h"
 #include "rt_raykey.h"
+#include "rt_wavefront.h"
 
 namespace rt {
 
@@ -45,6 +47,8 @@ void ray_stream_release(rt_scene* s) {
   }
   if (r.d_buf) (void)hipFree(r.d_buf);
   if (r.d_tmp) (void)hipFree(r.d_tmp);
+  if (r.d_wf) (void)hipFree(r.d_wf);
+  if (r.d_counts) (void)hipFree(r.d_counts);
   r = rt_scene::RayScratch{};
 }
 
@@ -119,6 +123,24 @@ int enqueue_reorder(rt_scene* s, const RayParams& R, hipStream_t st, const uint3
   return RT_OK;
 }
 
+// RT_RAYS_REORDER of a list call on st: R.perm for a list beyond one packet, and the record rt_debug_ray_order reads
+int begin_reorder(rt_scene* s, RayParams& R, hipStream_t st) {
+  const bool sorted = R.n > 64;  // up to 64 rays are one packet in any order
+  int rc;
+  if (sorted && (rc = enqueue_reorder(s, R, st, &R.perm))) return rc;
+  s->rays.last_n = R.n;
+  s->rays.last_sorted = sorted;
+  return RT_OK;
+}
+
+// RT_RAYS_STATS of a list call on st: the scene's counters, cleared, as the kernels' P.stats
+int begin_stats(rt_scene* s, FrameParams& P, hipStream_t st) {
+  P.stats = s->d_stats;
+  HIPCHECK(hipMemsetAsync(s->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
+  s->last_flags = RT_FRAME_STATS;  // rt_debug_counters reads these counters
+  return RT_OK;
+}
+
 // the packet kernels of one query on st (R's pointers are device memory); flags: RT_RAYS_*
 int enqueue_rays(rt_scene* s, int query, int flags, RayParams R, const rt_light* lights, int32_t n_lights, hipStream_t st) {
   FrameParams P;
@@ -135,18 +157,8 @@ int enqueue_rays(rt_scene* s, int query, int flags, RayParams R, const rt_light*
     return RT_ERR_UNSUPPORTED;
   }
   int rc;
-  if (reorder) {
-    rt_scene::RayScratch& r = s->rays;
-    const bool sorted = R.n > 64;  // up to 64 rays are one packet in any order
-    if (sorted && (rc = enqueue_reorder(s, R, st, &R.perm))) return rc;
-    r.last_n = R.n;
-    r.last_sorted = sorted;
-  }
-  if (stats) {
-    P.stats = s->d_stats;
-    HIPCHECK(hipMemsetAsync(s->d_stats, 0, kStatSlots * sizeof(unsigned long long), st));
-    s->last_flags = RT_FRAME_STATS;  // rt_debug_counters reads these counters
-  }
+  if (reorder && (rc = begin_reorder(s, R, st))) return rc;
+  if (stats && (rc = begin_stats(s, P, st))) return rc;
   const int grid = (R.n + 255) / 256;
   if (w4) {
     VariantCall vc;
@@ -163,6 +175,141 @@ int enqueue_rays(rt_scene* s, int query, int flags, RayParams R, const rt_light*
     HIPCHECK(hipEventRecord((hipEvent_t)s->rays.ev, st));
     s->rays.last_stream = (void*)st;
   }
+  return RT_OK;
+}
+
+// ---- rt_trace_stream_color: traceRay at any depth and mode ----
+
+// the in-order (or level-0 reordered) list kernel k_rays_depth; P carries mode, depth and lights
+int enqueue_rays_depth(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st) {
+  const bool stats = (flags & RT_RAYS_STATS) != 0, reorder = (flags & RT_RAYS_REORDER) != 0;
+  int rc;
+  if (reorder && (rc = begin_reorder(s, R, st))) return rc;
+  if (stats && (rc = begin_stats(s, P, st))) return rc;
+  const int grid = (R.n + 255) / 256;
+  with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  HIPCHECK(hipGetLastError());
+  if (R.perm) {
+    HIPCHECK(hipEventRecord((hipEvent_t)s->rays.ev, st));
+    s->rays.last_stream = (void*)st;
+  }
+  return RT_OK;
+}
+
+// the wavefront state of n rays at D levels, carved from one allocation (rt_wavefront.h has the sizes)
+WfState wf_view(void* base, size_t n, int D) {
+  float* f = (float*)base;
+  auto take = [&](size_t words) { float* q = f; f += words; return q; };
+  WfState w;
+  w.o = take(3 * n), w.d = take(3 * n), w.hp = take(3 * n), w.hn = take(3 * n);
+  w.hmat = (int32_t*)take(n), w.hface = (uint32_t*)take(n);
+  w.ka = take(3 * n), w.kd = take(3 * n), w.ks = take(3 * n), w.ns = take(n);
+  w.face0 = (int32_t*)take(n), w.t0 = take(n), w.levels = (int32_t*)take(n);
+  w.direct = take(3 * n * (size_t)D);
+  w.list_a = (uint32_t*)take(n), w.list_b = (uint32_t*)take(n), w.key_a = (uint32_t*)take(n), w.key_b = (uint32_t*)take(n);
+  return w;
+}
+
+// room for the state of n rays at D levels; a growth waits for the previous use (as ensure_scratch)
+int ensure_wavefront(rt_scene* s, size_t n, int D) {
+  rt_scene::RayScratch& r = s->rays;
+  if (!r.ev) HIPCHECK(hipEventCreateWithFlags((hipEvent_t*)&r.ev, hipEventDisableTiming));
+  if (!r.d_counts && hipMalloc((void**)&r.d_counts, (RT_MAX_TRACE_DEPTH + 2) * sizeof(uint32_t)) != hipSuccess) {
+    (void)hipGetLastError();
+    r.d_counts = nullptr;
+    set_error("trace: device allocation failed");
+    return RT_ERR_NOMEM;
+  }
+  const size_t need = n * wf_bytes_per_ray(D);
+  if (need <= r.wf_bytes) return RT_OK;
+  HIPCHECK(hipEventSynchronize((hipEvent_t)r.ev));
+  const size_t want = std::max(std::max(need, 2 * r.wf_bytes), (size_t)4096 * wf_bytes_per_ray(2));
+  if (r.d_wf) (void)hipFree(r.d_wf);
+  r.d_wf = nullptr;
+  r.wf_bytes = 0;
+  if (hipMalloc(&r.d_wf, want) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("trace: device allocation failed");
+    return RT_ERR_NOMEM;
+  }
+  r.wf_bytes = want;
+  return RT_OK;
+}
+
+// RT_RAYS_WAVEFRONT: the stage kernels of every level, the regroups between them, the resolve pass -- all on st,
+// launched for the upper bound n (the live counts stay on the device)
+int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st) {
+  const int n = R.n, D = P.max_depth;
+  const bool stats = (flags & RT_RAYS_STATS) != 0, reorder = (flags & RT_RAYS_REORDER) != 0;
+  const bool sorting = reorder && n > 64;  // up to 64 rays are one packet in any order
+  const bool fused = !(P.shadows && P.n_lights > 0);  // no traversal in the shading
+  size_t tmp_sel = 0, tmp_sort = 0;
+  HIPCHECK(hipcub::DeviceSelect::Flagged(nullptr, tmp_sel, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                         (uint32_t*)nullptr, n, st));
+  HIPCHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_sort, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                              (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 32, st));
+  // every growth first, so that nothing is freed under work this call has enqueued
+  int rc = ensure_scratch(s, sorting ? (size_t)n : 0, std::max(tmp_sel, tmp_sort));
+  if (rc) return rc;
+  if ((rc = ensure_wavefront(s, (size_t)n, D))) return rc;
+  rt_scene::RayScratch& r = s->rays;
+  if (r.last_stream && r.last_stream != (void*)st) HIPCHECK(hipStreamWaitEvent(st, (hipEvent_t)r.ev, 0));
+  // level 0's order is the plain RT_RAYS_REORDER call's, kept for rt_debug_ray_order
+  if (reorder && (rc = begin_reorder(s, R, st))) return rc;
+  if (stats && (rc = begin_stats(s, P, st))) return rc;
+  hipLaunchKernelGGL(k_wf_counts, dim3(1), dim3(64), 0, st, r.d_counts, (uint32_t)n);
+  HIPCHECK(hipGetLastError());
+  r.last_levels = D;
+  WfParams W{};
+  W.s = wf_view(r.d_wf, (size_t)n, D);
+  W.counts = r.d_counts;
+  W.bounds = sorting ? (const float*)scratch_view(r).bounds : nullptr;
+  W.n = n, W.D = D;
+  W.origin_major = (kernel_variant() & VB_RAYKEY_ORIGIN_MAJOR) ? 1 : 0;
+  const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+  // the entries `in` marked by the last stage (W.s.key_a: keys or flags) -> the other list
+  auto regroup = [&](const uint32_t*& in) -> int {
+    uint32_t* out = in == W.s.list_b ? W.s.list_a : W.s.list_b;
+    size_t tb = r.tmp_bytes;
+    if (sorting) {  // stable: equal keys keep the order of `in`
+      HIPCHECK(hipcub::DeviceRadixSort::SortPairs(r.d_tmp, tb, (const uint32_t*)W.s.key_a, W.s.key_b, in, out, n, 0, 32, st));
+    } else if (in) {
+      HIPCHECK(hipcub::DeviceSelect::Flagged(r.d_tmp, tb, in, (const uint32_t*)W.s.key_a, out, r.d_counts + RT_MAX_TRACE_DEPTH + 1, n, st));
+    } else {
+      HIPCHECK(hipcub::DeviceSelect::Flagged(r.d_tmp, tb, hipcub::CountingInputIterator<uint32_t>(0u), (const uint32_t*)W.s.key_a, out,
+                                             r.d_counts + RT_MAX_TRACE_DEPTH + 1, n, st));
+    }
+    in = out;
+    return RT_OK;
+  };
+  const uint32_t* in = R.perm;  // level 0: the list as given, or its coherence order
+  for (int d = 0; d < D; d++) {
+    const bool last = d + 1 == D;
+    W.level = d;
+    W.ro = d ? W.s.o : R.o;
+    W.rd = d ? W.s.d : R.d;
+    W.list = in;
+    if (fused) {
+      W.mark = last ? nullptr : W.s.key_a;
+      with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, true, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
+      HIPCHECK(hipGetLastError());
+      if (!last && (rc = regroup(in))) return rc;
+      continue;
+    }
+    W.mark = W.s.key_a;
+    with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, false, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
+    HIPCHECK(hipGetLastError());
+    if ((rc = regroup(in))) return rc;  // the hits, for the shade stage
+    W.list = in;
+    W.mark = (sorting && !last) ? W.s.key_a : nullptr;  // without a sort the hit list is the next level's list
+    with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value>), grid, block, 0, st, P, W); }, stats);
+    HIPCHECK(hipGetLastError());
+    if (W.mark && (rc = regroup(in))) return rc;
+  }
+  hipLaunchKernelGGL(k_wf_resolve, grid, block, 0, st, P, W, R.rgb, R.face, R.t);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipEventRecord((hipEvent_t)r.ev, st));
+  r.last_stream = (void*)st;
   return RT_OK;
 }
 
@@ -318,6 +465,72 @@ extern "C" int rt_trace_stream(rt_scene* s, int32_t query, int32_t flags, const 
   if (hip_stream) return RT_OK;
   HIPCHECK(hipStreamSynchronize(st));
   return check_prefetch_word(s);
+}
+
+extern "C" int rt_trace_stream_color(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light* lights,
+                                     int32_t n_lights, int32_t mode, int32_t max_depth, void* hip_stream) {
+  // argument checks that need no device come first
+  if (!s) { set_error("null scene"); return RT_ERR_INVALID; }
+  if (mode != RT_MODE_PRIMARY && mode != RT_MODE_FULL) { set_error("rt_trace_stream_color: bad mode %d", mode); return RT_ERR_INVALID; }
+  if (max_depth < 0 || max_depth > RT_MAX_TRACE_DEPTH) {
+    set_error("rt_trace_stream_color: max_depth %d outside 0..%d", max_depth, RT_MAX_TRACE_DEPTH);
+    return RT_ERR_INVALID;
+  }
+  if (flags & ~(RT_RAYS_REORDER | RT_RAYS_STATS | RT_RAYS_WAVEFRONT)) {
+    set_error("rt_trace_stream_color: bad flags %d", flags);
+    return RT_ERR_INVALID;
+  }
+  if (!rays || rays->n < 0) { set_error("rt_trace_stream_color: invalid arguments"); return RT_ERR_INVALID; }
+  const int32_t n = rays->n;
+  if (n > 0) {
+    if (!rays->a3 || !rays->b3 || check_lights(lights, n_lights)) { set_error("rt_trace_stream_color: invalid arguments"); return RT_ERR_INVALID; }
+    if (!rays->rgb3) { set_error("rt_trace_stream_color: needs rgb3"); return RT_ERR_INVALID; }
+  }
+  int rc = check_device_scene(s);
+  if (rc) return rc;
+  if (n == 0) return RT_OK;
+  RayParams R{};
+  R.n = n;
+  R.o = rays->a3, R.d = rays->b3;
+  R.face = rays->face, R.t = rays->t, R.rgb = rays->rgb3;
+  const struct { const void* p; const char* what; } ptrs[] = {{R.o, "a3"}, {R.d, "b3"}, {R.face, "face"}, {R.t, "t"}, {R.rgb, "rgb3"}};
+  for (const auto& q : ptrs)
+    if ((rc = check_device_pointer(s, q.p, "rt_trace_stream_color", q.what))) return rc;
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)s->stream;
+  const int depth = max_depth > 0 ? max_depth : (mode == RT_MODE_FULL ? 2 : 1);
+  const bool wavefront = (flags & RT_RAYS_WAVEFRONT) != 0;
+  if (mode == RT_MODE_FULL && depth == 2 && !wavefront) {  // the existing RT_RAYS_COLOR path, same kernel
+    rc = enqueue_rays(s, Q_COLOR, flags, R, lights, n_lights, st);
+  } else {
+    FrameParams P;
+    fill_scene_params(s, P);
+    fill_lights(P, lights, n_lights);
+    P.mode = mode, P.max_depth = depth, P.shadows = mode == RT_MODE_FULL ? 1 : 0;
+    if (pick_trav(kernel_variant(), P.sc.n_nodes4 > 0) == TRAV_W4) {
+      set_error("rt_trace_stream_color: only the binary-tree kernels trace this mode / depth / flag, not kernel variant %d", kernel_variant());
+      return RT_ERR_UNSUPPORTED;
+    }
+    rc = wavefront ? enqueue_wavefront(s, flags, R, P, st) : enqueue_rays_depth(s, flags, R, P, st);
+  }
+  if (rc) return rc;
+  if (hip_stream) return RT_OK;
+  HIPCHECK(hipStreamSynchronize(st));
+  return check_prefetch_word(s);
+}
+
+extern "C" int rt_debug_ray_levels(rt_scene* s, int32_t capacity, int64_t* out2, int32_t* n_levels) {
+  int rc = check_device_scene(s);
+  if (rc) return rc;
+  const rt_scene::RayScratch& r = s->rays;
+  if (r.last_levels < 0) { set_error("rt_debug_ray_levels: no RT_RAYS_WAVEFRONT call yet"); return RT_ERR_INVALID; }
+  if (n_levels) *n_levels = r.last_levels;
+  if (!out2) return RT_OK;
+  if (capacity < r.last_levels) { set_error("rt_debug_ray_levels: buffer too small"); return RT_ERR_INVALID; }
+  HIPCHECK(hipEventSynchronize((hipEvent_t)r.ev));
+  uint32_t c[RT_MAX_TRACE_DEPTH + 1];
+  HIPCHECK(hipMemcpy(c, r.d_counts, sizeof(c), hipMemcpyDeviceToHost));
+  for (int d = 0; d < r.last_levels; d++) out2[2 * d] = c[d], out2[2 * d + 1] = c[d + 1];
+  return RT_OK;
 }
 
 extern "C" int rt_rays_camera(rt_scene* s, const rt_camera* cam, int32_t width, int32_t height, float* origins3_device,

@@ -255,6 +255,12 @@ struct rt_scene {
     void* last_stream = nullptr;
     int64_t last_n = -1;         // rays of the last RT_RAYS_REORDER call (-1: none yet)
     bool last_sorted = false;    // false: that call was one packet (n <= 64), traced in the given order
+    // RT_RAYS_WAVEFRONT (rt_wavefront.h): the per-ray state of the stage kernels, 124 + 12 D bytes per ray, and
+    // the level counts (counts[0] = n, counts[d + 1] = hits of level d), which rt_debug_ray_levels reads
+    void* d_wf = nullptr;
+    size_t wf_bytes = 0;
+    uint32_t* d_counts = nullptr;
+    int32_t last_levels = -1;    // D of the last RT_RAYS_WAVEFRONT call (-1: none yet)
   } rays;
   float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
   bool ray_bounds_valid = false;

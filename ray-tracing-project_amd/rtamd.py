@@ -26,6 +26,7 @@ RT_RAYS_SHADOW = 1
 RT_RAYS_COLOR = 2
 RT_RAYS_REORDER = 1
 RT_RAYS_STATS = 2
+RT_RAYS_WAVEFRONT = 4  # rt_trace_stream_color only
 
 # Every symbol include/rt/rt_api.h declares (checked by tests/test_abi.py)
 EXPORTS = [
@@ -42,6 +43,7 @@ EXPORTS = [
     "rt_debug_record_layout", "rt_debug_scene_flags", "rt_debug_env_knobs", "rt_debug_tree_cost",
     "rt_synchronize_devices", "rt_debug_lpt_stats", "rt_debug_wave_stats", "rt_debug_frame_plan",
     "rt_trace_stream", "rt_rays_camera", "rt_scene_ray_bounds", "rt_debug_ray_keys", "rt_debug_ray_order",
+    "rt_trace_stream_color", "rt_debug_ray_levels",
 ]
 RT_MAX_DEVICES = 16
 RT_DEVICES_ALL = -1
@@ -205,6 +207,9 @@ def lib():
             L.rt_scene_ray_bounds.argtypes = [vp, vp]
             L.rt_debug_ray_keys.argtypes = [C.c_int32, C.c_int32, vp, vp, vp, vp]
             L.rt_debug_ray_order.argtypes = [vp, C.c_int64, vp, C.POINTER(C.c_int64)]
+        if hasattr(L, "rt_trace_stream_color"):
+            L.rt_trace_stream_color.argtypes = [vp, C.c_int32, C.POINTER(RayStream), vp, C.c_int32, C.c_int32, C.c_int32, vp]
+            L.rt_debug_ray_levels.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int32)]
         _lib = L
     return _lib
 
@@ -609,6 +614,45 @@ class Scene:
         flags = (RT_RAYS_REORDER if reorder else 0) | (RT_RAYS_STATS if stats else 0)
         check(lib().rt_trace_stream(self.h, query, flags, C.byref(rs), C.cast(L, C.c_void_p), len(lights), _stream_ptr(stream)))
         return res
+
+    def trace_stream_color(self, a, b, lights, *, mode=RT_MODE_FULL, max_depth=0, reorder=False, wavefront=False,
+                           stats=False, stream=None, out=None):
+        """rt_trace_stream_color on device tensors: traceRay's colour of the rays a (origins), b (directions),
+        float32 [n,3], in mode (RT_MODE_PRIMARY / RT_MODE_FULL) at max_depth (0 = the mode's own) -- what render()
+        gives a pixel with that camera ray. Returns a dict of device tensors rgb, face, t (out, stream, reorder, stats:
+        as trace_stream). wavefront: RT_RAYS_WAVEFRONT, level by level with the rays regrouped between the stages
+        (same bits; then ray_levels() has the per-level counts)."""
+        n = _device_rays(a, "a")
+        if _device_rays(b, "b") != n:
+            raise ValueError("trace_stream_color: a and b differ in length")
+        given = dict(out or {})
+        res = {}
+        for name, dtype, width, required in self._STREAM_OUTPUTS[RT_RAYS_COLOR]:
+            x = given.pop(name, None)
+            if x is None and (required or out is None):
+                x = _torch_empty(a, (n, 3) if width == 3 else (n,), dtype)
+            if x is not None:
+                _check_device_array(x, dtype, (n, 3) if width == 3 else (n,), name)
+                res[name] = x
+        if given:
+            raise ValueError(f"trace_stream_color: unknown outputs {sorted(given)}")
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        rs = RayStream(n, a.data_ptr(), b.data_ptr(), ptr("face"), ptr("t"), None, None, None, ptr("rgb"))
+        lights = lights if lights is not None else []
+        L = self._lights(lights)
+        flags = (RT_RAYS_REORDER if reorder else 0) | (RT_RAYS_STATS if stats else 0) | (RT_RAYS_WAVEFRONT if wavefront else 0)
+        check(lib().rt_trace_stream_color(self.h, flags, C.byref(rs), C.cast(L, C.c_void_p), len(lights), mode, max_depth,
+                                          _stream_ptr(stream)))
+        return res
+
+    def ray_levels(self):
+        """The levels of the last wavefront=True call (rt_debug_ray_levels): int64 [D, 2], row d = (rays that entered
+        level d's closest-hit stage, how many of them hit)."""
+        n = C.c_int32(0)
+        check(lib().rt_debug_ray_levels(self.h, 0, None, C.byref(n)))
+        out = np.zeros((n.value, 2), np.int64)
+        check(lib().rt_debug_ray_levels(self.h, n.value, _p(out), C.byref(n)))
+        return out
 
     def camera_rays(self, cam, W, H, stream=None, out=None):
         """rt_rays_camera: the frame's primary rays as device tensors (origins [W*H,3], directions [W*H,3]),
