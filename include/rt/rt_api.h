@@ -490,6 +490,59 @@ int rt_debug_ray_levels(rt_scene* s, int32_t capacity, int64_t* out2, int32_t* n
 /* After an RT_RAYS_WAVEFRONT | RT_RAYS_REORDER call rt_debug_ray_order returns level 0's order, the permutation
  * the plain RT_RAYS_REORDER call computes for that list; a wavefront call without the reorder leaves it alone. */
 
+/* ---------------------------------------------------------------------------------------------
+ * Light sets: frames and ray lists lit by any number of lights (feature test: RT_HAS_LIGHT_SETS; the API
+ * version stays 4). Flyscene::lights / dirLights are unbounded vectors (flyscene.hpp:132-135; sphericalLight,
+ * flyscene.cpp:529-538, adds nLightpoints + 1 of them at a time) and calculateColor loops over all of them
+ * (:603-614). rt_render and its siblings carry at most RT_MAX_LIGHTS lights in the kernel arguments and keep
+ * that cap; a light set holds up to RT_MAX_LIGHT_SET lights in device memory.
+ *
+ * rt_light_set_create(s, lights, n_lights, out)
+ *   Copies n_lights lights from host memory in the order calculateColor applies them -- every point light in
+ *   array order, then every directional light in array order; kind: anything that is not RT_LIGHT_DIRECTIONAL
+ *   is a point light -- and uploads one copy to each device of the scene (devices[0..] of a multi-device
+ *   scene). The set is immutable and belongs to s, so frames in flight cannot race with it. n_lights == 0 is a
+ *   valid, empty set. n_lights < 0 or > RT_MAX_LIGHT_SET, n_lights > 0 with lights NULL, a NULL scene or out:
+ *   RT_ERR_INVALID. On a host-only scene (RT_DEVICE_NONE) the set holds the host copy only: create, get and
+ *   destroy work, rendering with it returns RT_ERR_NO_DEVICE.
+ * rt_light_set_get(ls, capacity, out, n_out)
+ *   The set's lights in the set's order; *n_out (may be NULL) = their number. out NULL: the count only.
+ *   capacity smaller than the count: RT_ERR_INVALID, nothing written.
+ * rt_light_set_destroy(ls)
+ *   Waits for the scene's own streams (every device's frame slots), then frees the set. Sets still alive when
+ *   their scene is destroyed are freed by rt_scene_destroy; such a handle must not be used afterwards. A set
+ *   used by work enqueued on a caller's stream (rt_trace_stream_lit with hip_stream) must outlive that work:
+ *   the library cannot wait for a stream it does not own, exactly as for the rt_ray_stream buffers.
+ *
+ * rt_render_lit / rt_render_lit_async: rt_render / rt_render_async with the set in place of lights, n_lights.
+ *   Every mode, max_depth, shard, flag, rt_synchronize, the downloads and multi-device scenes behave as for
+ *   rt_render; a pixel's colour, face and t are traceRay's with Flyscene::lights and dirLights equal to the set
+ *   (RT_MODE_BOX_COLORS ignores lights). A set of another scene: RT_ERR_INVALID.
+ *   A set of at most RT_MAX_LIGHTS lights is copied into the kernel arguments and takes exactly rt_render's
+ *   path. A larger set is read from device memory by the generic traceRay kernel (k_render_depth; scalar loads
+ *   indexed by the wave-uniform light number, the same arithmetic in the same order, hence the same bits as
+ *   the kernel-argument path for the same lights), for PRIMARY and FULL at every depth; that kernel keeps no
+ *   per-wave counts, so RT_FRAME_WAVE_STATS is refused there (RT_ERR_UNSUPPORTED).
+ * rt_trace_stream_lit: rt_trace_stream_color with the set: the same flags (RT_RAYS_REORDER | RT_RAYS_STATS |
+ *   RT_RAYS_WAVEFRONT), checks, stream semantics and handling of n == 0 and host-only scenes. Ray i gets exactly
+ *   the values rt_render_lit writes for a pixel with that camera ray. Under RT_RAYS_WAVEFRONT | RT_RAYS_REORDER
+ *   the shade stage's key uses the set's first light. Lists read the copy on the scene's device (devices[0]).
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_LIGHT_SETS 1
+#define RT_MAX_LIGHT_SET 65536
+typedef struct rt_light_set rt_light_set;
+
+int rt_light_set_create(rt_scene* s, const rt_light* lights, int32_t n_lights, rt_light_set** out);
+void rt_light_set_destroy(rt_light_set* ls);
+int rt_light_set_get(const rt_light_set* ls, int32_t capacity, rt_light* out, int32_t* n_out);
+
+int rt_render_lit(rt_scene* s, const rt_camera* cam, const rt_light_set* ls, const rt_frame* frame, float* out_rgb,
+                  rt_stats* stats);
+int rt_render_lit_async(rt_scene* s, const rt_camera* cam, const rt_light_set* ls, const rt_frame* frame);
+
+int rt_trace_stream_lit(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light_set* ls,
+                        int32_t mode, int32_t max_depth, void* hip_stream);
+
 /* createDebugRay (flyscene.cpp:129-173) without the GL cylinders: the camera ray through a
  * (float) mouse position and its reflection chain, up to max_depth segments; every segment carries the
  * first ray's traceRay colour; a miss ends the chain with a 10-unit segment. *n_out = segments written. */
@@ -541,7 +594,9 @@ int rt_debug_record_layout(int64_t n_nodes, int64_t n_tris, int64_t n_wide, int6
  * every kernel and block-order decision), with the dispatch knobs at their defaults.
  * in[0..10] (n_in = 11): mode, max_depth, flags, tiles_x, tiles_y (16x16-pixel tiles of the frame), shard_index,
  * shard_count (>= 1), kernel variant, bytes of the scene's binary node + triangle records, whether the scene has
- * the quantised 4-wide tree, whether no other frame of the scene is in flight.
+ * the quantised 4-wide tree, whether no other frame of the scene is in flight. n_in = 12 adds in[11] = the number
+ * of lights the frame reads from a light set in device memory (0 = none, the 11-input plan): non-zero selects the
+ * generic-depth kernel for PRIMARY and FULL at every depth.
  * out[0..13] (n_out = 14): 0 kernel (0 none: empty shard, 1 generic depth, 2 PRIMARY fused, 3 PRIMARY trace +
  * shade, 4 PRIMARY dual, 5 PRIMARY two rays per lane, 6 PRIMARY persistent, 7 FULL megakernel, 8 FULL pipeline),
  * 1 traversal flavour (0 VGPR stack, 1 LDS stack, 2 quantised 4-wide), 2 needs the variants library, 3 the
@@ -564,7 +619,10 @@ int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origi
  * longest-first dispatch knobs (524288, longest-first also with frames in flight, is A/B only: the frames share
  * one order, which one of them may read while another's sort rewrites it, and then skip or repeat waves),
  * 2097152 PRIMARY packets on the binary tree, 4194304 the origin-major layout of the ray streams' coherence key
- * (rt_debug_ray_keys follows it). Bits of the variants library
+ * (rt_debug_ray_keys follows it), 8388608 light sets read from device memory at any count (by default only sets
+ * beyond RT_MAX_LIGHTS are; lets the tests compare the two paths at 0, 1 and 32 lights; a set of 0 lights has no
+ * light to read and keeps the default kernels), 16777216 the memory-lights kernels without the wave-level occluder
+ * cache of their shadow packets (A/B and tests). Bits of the variants library
  * only (make variants -> librtamd_variants.so; the product library's rt_render returns
  * RT_ERR_UNSUPPORTED for them): 1 VGPR wave stack, 2 4-wide quantised BVH (scenes of the host builders,
  * which also build that tree), 16 FULL as a stage pipeline (whole frames only: a sharded frame returns

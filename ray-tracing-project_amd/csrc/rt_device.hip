@@ -873,7 +873,35 @@ int device_replicate(rt_scene* s) {
 
 }  // namespace rt
 
-rt_scene::~rt_scene() { rt::device_release(this); }
+// frees a light set's device copies (dev[k] lives on replica k's device) and the set; the caller has drained the
+// streams that may read it
+static void free_light_set(rt_light_set* ls) {
+  rt_scene* s = ls->scene;
+  for (size_t k = 0; k < ls->dev.size(); k++) {
+    if (!ls->dev[k]) continue;
+    const rt_scene* r = k == 0 ? s : s->replicas[k - 1].get();
+    (void)hipSetDevice(r->device);
+    (void)hipFree(ls->dev[k]);
+  }
+  if (!ls->dev.empty() && s->device != RT_DEVICE_NONE) (void)hipSetDevice(s->device);
+  delete ls;
+}
+
+rt_scene::~rt_scene() {
+  if (!light_sets.empty()) {  // sets still alive go with their scene, once every device's frames have finished
+    rt::stop_workers(this);
+    for (size_t k = 0; k <= replicas.size(); k++) {
+      rt_scene* r = k == 0 ? this : replicas[k - 1].get();
+      if (r->device == RT_DEVICE_NONE) continue;
+      (void)hipSetDevice(r->device);
+      for (int i = 0; i < r->n_slots; i++)
+        if (r->slots[i].stream) (void)hipStreamSynchronize((hipStream_t)r->slots[i].stream);
+    }
+    for (rt_light_set* ls : light_sets) free_light_set(ls);
+    light_sets.clear();
+  }
+  rt::device_release(this);
+}
 
 namespace rt {
 
@@ -1116,6 +1144,21 @@ void rt::fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights) {
     }
 }
 
+// A light set on the path the variant selects: at most RT_MAX_LIGHTS lights travel in the kernel arguments and take
+// exactly rt_render's path (the host copy is already in calculateColor's order, which fill_lights keeps); more
+// -- or any number but none under VB_MEM_LIGHTS -- are read from replica `rep`'s device array.
+int rt::fill_light_set(FrameParams& P, const rt_light_set* ls, int rep) {
+  const int32_t n = (int32_t)ls->host.size();
+  const int v = kernel_variant();
+  if (n <= RT_MAX_LIGHTS && !((v & VB_MEM_LIGHTS) && n > 0)) {
+    fill_lights(P, ls->host.data(), n);
+    return LS_KERNARG;
+  }
+  P.n_lights = n;
+  P.light_set = ls->dev[(size_t)rep];
+  return (v & VB_NO_OCCLUDER_CACHE) ? LS_MEMORY : LS_MEMORY_CACHED;
+}
+
 // camera (camera.hpp:115-118,155-173,263-266) and lights of a frame; P.Minv is set (fill_scene_params)
 void rt::fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights) {
   affinv(cam->view_matrix, P.vinv);
@@ -1254,9 +1297,16 @@ static int launch_frame(const FramePlan& plan, rt_scene* s, rt_scene::FrameSlot&
   VariantCall vc;
   switch (plan.kernel) {
     case FK_NONE: break;
-    case FK_GENERIC_DEPTH:  // one 8x8 wave per block
-      with_bools([&](auto S, auto H) { hipLaunchKernelGGL((k_render_depth<S.value, H.value>), dim3(grid * 4), dim3(64), 0, st, P); },
-                 stats, hits);
+    case FK_GENERIC_DEPTH:  // one 8x8 wave per block; a light set in device memory: its own instantiations
+      if (plan.light_source == LS_MEMORY_CACHED)
+        with_bools([&](auto S, auto H) { hipLaunchKernelGGL((k_render_depth<S.value, H.value, LS_MEMORY_CACHED>), dim3(grid * 4), dim3(64), 0, st, P); },
+                   stats, hits);
+      else if (plan.light_source == LS_MEMORY)
+        with_bools([&](auto S, auto H) { hipLaunchKernelGGL((k_render_depth<S.value, H.value, LS_MEMORY>), dim3(grid * 4), dim3(64), 0, st, P); },
+                   stats, hits);
+      else
+        with_bools([&](auto S, auto H) { hipLaunchKernelGGL((k_render_depth<S.value, H.value>), dim3(grid * 4), dim3(64), 0, st, P); },
+                   stats, hits);
       break;
     case FK_PRIMARY_DUAL:
       vc.P = P, vc.units = plan.units, vc.st = st, vc.hits = hits, vc.boxcol = boxcol;
@@ -1341,8 +1391,12 @@ static void note_frame(rt_scene* s, int slot_id, const rt_frame* fr, const Frame
 }
 
 // one device's share of a frame (the whole frame on a single-device scene; a replica's shard otherwise)
-static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr) {
+// ls (rt_render_lit): the frame's lights are that set's instead of lights / n_lights; rep = this replica's index in
+// the set's device copies
+static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr,
+                      const rt_light_set* ls = nullptr, int rep = 0) {
   int rc = check_device_scene(s);
+  if (ls) lights = nullptr, n_lights = 0;
   if (rc || (rc = check_frame_args(cam, lights, n_lights, fr))) return rc;
   const int sc = fr->shard_count > 0 ? fr->shard_count : 1, si = fr->shard_index;
   if (fr->mode == RT_MODE_BOX_COLORS && (rc = ensure_face_boxcolor(s))) return rc;
@@ -1355,6 +1409,8 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
   FrameParams P;
   fill_scene_params(s, P);
   fill_camera_lights(P, cam, lights, n_lights);
+  // (a box-colours frame ignores lights: none are handed to its kernel, whatever the set holds)
+  const int light_source = (ls && fr->mode != RT_MODE_BOX_COLORS) ? fill_light_set(P, ls, rep) : LS_KERNARG;
   P.W = fr->width, P.H = fr->height, P.tiles_x = (fr->width + 15) / 16, P.tiles_y = (fr->height + 15) / 16;
   P.shard_index = si, P.shard_count = sc, P.super_tile = frame_super_tile(sc);
   P.mode = fr->mode, P.flags = fr->flags, P.shadows = fr->mode == RT_MODE_FULL ? 1 : 0;
@@ -1371,6 +1427,8 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
   in.tiles_x = P.tiles_x, in.tiles_y = P.tiles_y, in.shard_index = si, in.shard_count = sc;
   in.variant = kernel_variant(), in.has_wide4 = P.sc.n_nodes4 > 0;
   in.record_bytes = (uint64_t)(s->hs.nodes.size() + s->hs.tris.size()) * 64;
+  in.mem_lights = light_source == LS_KERNARG ? 0 : P.n_lights;
+  in.occluder_cache = light_source != LS_MEMORY;
   // a frame alone on the GPU: no other frame of this scene in flight (the block order and the longest-first
   // order depend on it)
   for (int k = 0; k < s->n_slots; k++)
@@ -1394,7 +1452,8 @@ static int render_one(rt_scene* s, const rt_camera* cam, const rt_light* lights,
   if ((fr->flags & RT_FRAME_STATS) && (fr->flags & RT_FRAME_WAVE_STATS)) {  // per logical wave (tile * 4 + quarter)
     // the generic traceRay kernel writes no per-wave records: refuse the frame instead of returning all-zero records
     if (!plan.writes_wave_stats) {
-      set_error("rt_render: RT_FRAME_WAVE_STATS needs the mode's own max_depth (the generic-depth kernel keeps no per-wave counts)");
+      set_error(in.mem_lights ? "rt_render_lit: RT_FRAME_WAVE_STATS is not available with a light set read from device memory (the generic-depth kernel keeps no per-wave counts)"
+                              : "rt_render: RT_FRAME_WAVE_STATS needs the mode's own max_depth (the generic-depth kernel keeps no per-wave counts)");
       return RT_ERR_UNSUPPORTED;
     }
     const size_t lw = (size_t)plan.grid * 4;
@@ -1520,6 +1579,8 @@ struct EnqueueWorker {
   rt_camera cam;
   rt_light lights[RT_MAX_LIGHTS];
   int32_t n_lights = 0;
+  const rt_light_set* ls = nullptr;  // rt_render_lit: the frame's light set (then n_lights = 0), replica `rep`'s copy
+  int rep = 0;
   rt_frame fr;
   int rc = RT_OK;
   std::string err;
@@ -1539,7 +1600,7 @@ static void worker_loop(EnqueueWorker* w) {
       if (w->quit && w->posted.load(std::memory_order_acquire) == seen) return;
     }
     seen = w->posted.load(std::memory_order_acquire);
-    w->rc = render_one(w->r, &w->cam, w->n_lights ? w->lights : nullptr, w->n_lights, &w->fr);
+    w->rc = render_one(w->r, &w->cam, w->n_lights ? w->lights : nullptr, w->n_lights, &w->fr, w->ls, w->rep);
     if (w->rc) w->err = rt_last_error();
     w->done.store(seen, std::memory_order_release);
     { std::lock_guard<std::mutex> lk(w->mu); }
@@ -1565,6 +1626,7 @@ static int start_workers(rt_scene* s) {
   for (auto& r : s->replicas) {
     auto w = std::make_shared<EnqueueWorker>();
     w->r = r.get();
+    w->rep = 1 + (int)s->workers.size();
     try {
       w->th = std::thread(worker_loop, w.get());
     } catch (const std::exception&) {
@@ -1583,7 +1645,9 @@ static int start_workers(rt_scene* s) {
 // shard (super-tile t: t % (sc*D) = si + sc*k  <=>  t % sc = si). Each replica renders on its own slot
 // streams, its launches queued by its own worker thread (replica 0's by the caller); nothing is exchanged
 // between devices.
-static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr) {
+static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr,
+                        const rt_light_set* ls = nullptr) {
+  if (ls) lights = nullptr, n_lights = 0;  // every replica reads its own copy of the set
   if (!fr || !cam || n_lights < 0 || n_lights > RT_MAX_LIGHTS || (n_lights && !lights)) {
     set_error("rt_render: invalid arguments");
     return RT_ERR_INVALID;
@@ -1607,7 +1671,7 @@ static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* light
   if (start_workers(s) != RT_OK) {  // (no helper threads: queue every device from this thread)
     for (int k = 0; k < D; k++) {
       const rt_frame f = shard_of(k);
-      const int rc = render_one(replica(s, k), cam, lights, n_lights, &f);
+      const int rc = render_one(replica(s, k), cam, lights, n_lights, &f, ls, k);
       if (rc) return rc;
     }
     HIPCHECK(hipSetDevice(s->device));
@@ -1620,6 +1684,7 @@ static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* light
       std::lock_guard<std::mutex> lk(w.mu);
       w.cam = *cam;
       w.n_lights = n_lights;
+      w.ls = ls;
       if (n_lights) memcpy(w.lights, lights, sizeof(rt_light) * (size_t)n_lights);
       w.fr = shard_of((int)k + 1);
       seq[k] = w.posted.load(std::memory_order_relaxed) + 1;
@@ -1628,7 +1693,7 @@ static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* light
     w.cv.notify_all();
   }
   const rt_frame f0 = shard_of(0);
-  int rc = render_one(s, cam, lights, n_lights, &f0);
+  int rc = render_one(s, cam, lights, n_lights, &f0, ls, 0);
   std::string err0 = rc ? rt_last_error() : "";
   for (size_t k = 0; k < s->workers.size(); k++) {  // every worker has queued its share before this returns
     EnqueueWorker& w = *s->workers[k];
@@ -1654,6 +1719,95 @@ extern "C" int rt_render_async(rt_scene* s, const rt_camera* cam, const rt_light
                                const rt_frame* fr) {
   if (s && !s->replicas.empty()) return render_multi(s, cam, lights, n_lights, fr);
   return render_one(s, cam, lights, n_lights, fr);
+}
+
+// ---- light sets (rt_api.h RT_HAS_LIGHT_SETS) ----
+
+extern "C" int rt_light_set_create(rt_scene* s, const rt_light* lights, int32_t n_lights, rt_light_set** out) {
+  if (out) *out = nullptr;
+  if (!s || !out || n_lights < 0 || n_lights > RT_MAX_LIGHT_SET || (n_lights && !lights)) {
+    set_error("rt_light_set_create: invalid arguments");
+    return RT_ERR_INVALID;
+  }
+  std::unique_ptr<rt_light_set> ls(new rt_light_set);
+  ls->scene = s;
+  // calculateColor's order, as fill_lights: every point light, then every directional light
+  ls->host.reserve((size_t)n_lights);
+  for (int pass = 0; pass < 2; pass++)
+    for (int32_t l = 0; l < n_lights; l++) {
+      const int kind = lights[l].kind == RT_LIGHT_DIRECTIONAL ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT;
+      if (kind != (pass ? RT_LIGHT_DIRECTIONAL : RT_LIGHT_POINT)) continue;
+      rt_light x = lights[l];
+      x.kind = kind;
+      ls->host.push_back(x);
+    }
+  if (s->device != RT_DEVICE_NONE) {
+    std::vector<Light> dl((size_t)n_lights);
+    for (int32_t l = 0; l < n_lights; l++) {
+      memcpy(dl[(size_t)l].p, ls->host[(size_t)l].position, 12);
+      memcpy(dl[(size_t)l].c, ls->host[(size_t)l].color, 12);
+      dl[(size_t)l].kind = ls->host[(size_t)l].kind;
+    }
+    const size_t bytes = std::max<size_t>(dl.size(), 1) * sizeof(Light);
+    const int D = n_replicas(s);
+    ls->dev.assign((size_t)D, nullptr);
+    int rc = RT_OK;
+    for (int k = 0; k < D && rc == RT_OK; k++) {
+      hipError_t e = hipSetDevice(replica(s, k)->device);
+      if (e == hipSuccess) e = hipMalloc((void**)&ls->dev[(size_t)k], bytes);
+      if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ls->dev[(size_t)k] = nullptr;
+        set_error("rt_light_set_create: device allocation failed (%s)", hipGetErrorString(e));
+        rc = RT_ERR_NOMEM;
+        break;
+      }
+      if (!dl.empty() && (e = hipMemcpy(ls->dev[(size_t)k], dl.data(), dl.size() * sizeof(Light), hipMemcpyHostToDevice)) != hipSuccess) {
+        set_error("rt_light_set_create: upload failed (%s)", hipGetErrorString(e));
+        rc = RT_ERR_HIP;
+      }
+    }
+    (void)hipSetDevice(s->device);
+    if (rc) {
+      free_light_set(ls.release());
+      return rc;
+    }
+  }
+  s->light_sets.push_back(ls.get());
+  *out = ls.release();
+  return RT_OK;
+}
+
+extern "C" void rt_light_set_destroy(rt_light_set* ls) {
+  if (!ls) return;
+  rt_scene* s = ls->scene;
+  // frames in flight on the scene's own streams may still read the set
+  for (int k = 0; k < n_replicas(s) && !ls->dev.empty(); k++) {
+    rt_scene* r = replica(s, k);
+    if (r->device == RT_DEVICE_NONE) continue;
+    (void)hipSetDevice(r->device);
+    for (int i = 0; i < r->n_slots; i++)
+      if (r->slots[i].stream) (void)hipStreamSynchronize((hipStream_t)r->slots[i].stream);
+  }
+  s->light_sets.erase(std::remove(s->light_sets.begin(), s->light_sets.end(), ls), s->light_sets.end());
+  free_light_set(ls);
+}
+
+extern "C" int rt_light_set_get(const rt_light_set* ls, int32_t capacity, rt_light* out, int32_t* n_out) {
+  if (!ls) { set_error("rt_light_set_get: null set"); return RT_ERR_INVALID; }
+  const int32_t n = (int32_t)ls->host.size();
+  if (out && capacity < n) { set_error("rt_light_set_get: buffer too small (%d lights)", n); return RT_ERR_INVALID; }
+  if (n_out) *n_out = n;
+  if (out && n) memcpy(out, ls->host.data(), sizeof(rt_light) * (size_t)n);
+  return RT_OK;
+}
+
+extern "C" int rt_render_lit_async(rt_scene* s, const rt_camera* cam, const rt_light_set* ls, const rt_frame* fr) {
+  if (!s) { set_error("null scene"); return RT_ERR_INVALID; }
+  if (!ls) { set_error("rt_render_lit: null light set"); return RT_ERR_INVALID; }
+  if (ls->scene != s) { set_error("rt_render_lit: the light set belongs to another scene"); return RT_ERR_INVALID; }
+  if (!s->replicas.empty()) return render_multi(s, cam, nullptr, 0, fr, ls);
+  return render_one(s, cam, nullptr, 0, fr, ls, 0);
 }
 
 extern "C" int rt_synchronize_devices(rt_scene* s, rt_stats* out, int32_t capacity, rt_stats* per_device) {
@@ -2128,10 +2282,25 @@ extern "C" int rt_frame_unpack_shards_rgb8(const void* packed_device, int32_t sh
   return RT_OK;
 }
 
+static int finish_render(rt_scene* s, const rt_frame* fr, float* out_rgb, rt_stats* stats);
+
+extern "C" int rt_render_lit(rt_scene* s, const rt_camera* cam, const rt_light_set* ls, const rt_frame* fr, float* out_rgb,
+                             rt_stats* stats) {
+  int rc = rt_render_lit_async(s, cam, ls, fr);
+  if (rc) return rc;
+  return finish_render(s, fr, out_rgb, stats);
+}
+
 extern "C" int rt_render(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* fr,
                          float* out_rgb, rt_stats* stats) {
   int rc = rt_render_async(s, cam, lights, n_lights, fr);
   if (rc) return rc;
+  return finish_render(s, fr, out_rgb, stats);
+}
+
+// the synchronous half of rt_render / rt_render_lit: waits for the frame just queued and copies it to out_rgb
+static int finish_render(rt_scene* s, const rt_frame* fr, float* out_rgb, rt_stats* stats) {
+  int rc;
   const int W = fr->width, H = fr->height;
   if (!s->replicas.empty() && out_rgb) {
     // multi-device: each device's tile packing and copy are queued right behind its share of the frame, and

@@ -55,6 +55,8 @@ struct FrameInputs {
   uint64_t record_bytes = 0;  // the scene's binary node + triangle records
   bool has_wide4 = false;     // the scene has the quantised 4-wide tree (DevScene::n_nodes4 > 0)
   bool alone = true;          // no other frame of this scene in flight
+  int mem_lights = 0;         // lights the frame reads from a light set in device memory (0 = none: kernel arguments)
+  bool occluder_cache = true; // ... with the wave-level occluder cache of its shadow packets (VB_NO_OCCLUDER_CACHE: off)
   // debug-environment knobs (RT_SPLIT_K, RT_SPLIT_KP, RT_TIMELINE_SPLIT), at their defaults unless set
   int split_k = kSplitK, split_kp = kSplitKPrimary;
   bool timeline_split = false;
@@ -76,6 +78,7 @@ struct FramePlan {
   bool lpt = false;              // dispatched longest-first (k_order_lpt)
   int split_ceiling = 0;         // FrameParams::split_k once the frame has an order (0: the kernel never splits)
   bool primary_binary_tree = false, lpt_coarse = false;  // VB_PRIMARY_BINARY_TREE, VB_COARSE_COST_BUCKETS
+  int light_source = LS_KERNARG; // k_render_depth's LSRC: LS_MEMORY_CACHED / LS_MEMORY for a light set in device memory
   int variant = 0;               // handed on to variant_launch: rt_variants.hip reads the pipeline's and persistent's sub-bits
 };
 
@@ -93,8 +96,12 @@ inline FramePlan plan_frame(const FrameInputs& in) {
   p.full_small_build = (v & VB_FULL_SMALL_BUILD) || (!(v & VB_FULL_8_WAVES) && p.l2_resident);
   p.primary_binary_tree = (v & VB_PRIMARY_BINARY_TREE) != 0;
   p.lpt_coarse = (v & VB_COARSE_COST_BUCKETS) != 0;
-  const bool generic = !boxcol && (p.depth != own_depth || (v & VB_GENERIC_DEPTH));
-  const bool dual = prim && !stats && (in.max_depth <= 1 || boxcol) && !(v & VB_DUAL_EXCLUDED) && (v & VB_DUAL_CHAIN);
+  // a light set in device memory is read by the generic kernel's memory-lights instantiations alone: PRIMARY and
+  // FULL at every depth (a box-colours frame has no lights and keeps its kernel)
+  const bool mem_lights = !boxcol && in.mem_lights > 0;
+  p.light_source = !mem_lights ? LS_KERNARG : in.occluder_cache ? LS_MEMORY_CACHED : LS_MEMORY;
+  const bool generic = !boxcol && (p.depth != own_depth || (v & VB_GENERIC_DEPTH) || mem_lights);
+  const bool dual = prim && !stats && (in.max_depth <= 1 || boxcol) && !(v & VB_DUAL_EXCLUDED) && (v & VB_DUAL_CHAIN) && !mem_lights;
   const bool lds = p.trav == TRAV_B2_LDS;
   FrameKernel k;
   if (generic) k = FK_GENERIC_DEPTH;

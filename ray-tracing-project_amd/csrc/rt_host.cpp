@@ -320,7 +320,7 @@ extern "C" int rt_debug_record_layout(int64_t n_nodes, int64_t n_tris, int64_t n
 }
 
 extern "C" int rt_debug_frame_plan(const int64_t in[], int32_t n_in, int32_t out[], int32_t n_out) {
-  if (!in || !out || n_in != 11 || n_out != 14 || in[3] <= 0 || in[4] <= 0 || in[3] > 65536 || in[4] > 65536 || in[6] < 1 ||
+  if (!in || !out || (n_in != 11 && n_in != 12) || n_out != 14 || (n_in == 12 && (in[11] < 0 || in[11] > RT_MAX_LIGHT_SET)) || in[3] <= 0 || in[4] <= 0 || in[3] > 65536 || in[4] > 65536 || in[6] < 1 ||
       in[5] < 0 || in[5] >= in[6] || in[8] < 0) {
     rt::set_error("rt_debug_frame_plan: bad argument");
     return RT_ERR_INVALID;
@@ -332,6 +332,7 @@ extern "C" int rt_debug_frame_plan(const int64_t in[], int32_t n_in, int32_t out
   fi.record_bytes = (uint64_t)in[8];
   fi.has_wide4 = in[9] != 0;
   fi.alone = in[10] != 0;
+  if (n_in == 12) fi.mem_lights = (int)in[11];  // lights read from a light set in device memory (0 = none)
   const rt::FramePlan p = rt::plan_frame(fi);
   const int32_t o[14] = {p.kernel, p.trav, p.needs_variants, p.grid, (int32_t)p.units, p.depth, p.l2_resident, p.xcd_remap,
                          p.writes_wave_stats, p.lpt, p.split_ceiling, p.rotate_bands, p.pipeline_buffers, p.full_small_build};

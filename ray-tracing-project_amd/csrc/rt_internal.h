@@ -22,6 +22,7 @@ struct uint2 { unsigned int x, y; };
 
 struct rt_scene;
 struct rt_light;
+struct rt_light_set;
 struct rt_camera;
 
 namespace rt {
@@ -97,6 +98,8 @@ enum VariantBit : int {
   VB_PRIMARY_BINARY_TREE = 2097152,  // PRIMARY packets on the binary tree instead of the fp32 4-wide tree
                                      // (traverse_wide_fast)
   VB_RAYKEY_ORIGIN_MAJOR = 4194304,  // ray streams: the origin-major key layout instead of octant-major (rt_raykey.h)
+  VB_MEM_LIGHTS = 8388608,           // light sets: read the lights from device memory at any count (default: > 32)
+  VB_NO_OCCLUDER_CACHE = 16777216,   // the memory-lights kernels without the wave-level occluder cache (A/B, tests)
   // PRIMARY variants that leave the fused kernel
   VB_PRIMARY_UNFUSED = VB_SPLIT_PRIMARY | VB_TWO_RAYS_PER_LANE | VB_PERSISTENT,
   // bits under which VB_DUAL_CHAIN is ignored
@@ -303,6 +306,9 @@ struct FrameParams {
   // grid is then (logical waves + 3 split_k) blocks. 0 = off.
   int32_t split_k;
   const float* face_boxcolor;  // RT_MODE_BOX_COLORS: [n_faces][4] summed box colours per face id
+  // light sets beyond the 32 kernel-argument entries (rt_light_set): n_lights lights in device memory, in
+  // calculateColor's order, read by the memory-lights instantiations only (rt_kernels.h set_light); else null
+  const Light* light_set;
 };
 
 // Ray-list query parameters (rt_trace_closest / rt_trace_shadow)
@@ -325,6 +331,12 @@ struct RayParams {
 int check_device_scene(rt_scene* s);  // RT_ERR_NO_DEVICE for a host-only scene; makes the scene's device current
 void fill_scene_params(const rt_scene* s, FrameParams& P);  // clears P, then the scene's part of it
 void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights);
+// where the lights of a frame or list come from: kernel arguments, a light set's device array, and there with or
+// without the occluder cache (calc_color's LSRC)
+enum LightSource { LS_KERNARG = 0, LS_MEMORY = 1, LS_MEMORY_CACHED = 2 };
+// a light set on the path the current variant selects: LS_KERNARG copies it into P.lights (at most RT_MAX_LIGHTS),
+// otherwise P.light_set is replica `rep`'s device array; returns the LightSource
+int fill_light_set(FrameParams& P, const rt_light_set* ls, int rep);
 // camera and lights of a frame; P.Minv is set (fill_scene_params)
 void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights);
 int check_prefetch_word(rt_scene* s);  // RT_CHECK_PREFETCH debug build; RT_OK otherwise

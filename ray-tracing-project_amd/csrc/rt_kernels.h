@@ -329,13 +329,23 @@ __device__ __forceinline__ uint64_t accept_candidate(const DevScene& P, const Tr
   return cand & (ins | ballot(ref_box_test(P, r, bx)));
 }
 
+// The wave-level occluder cache of the memory-lights kernels (calc_color): the triangle slots at which lanes of
+// this wave last became blocked, most recent first; kOccNone = empty
+constexpr int kOccK = 2;
+constexpr uint32_t kOccNone = 0xFFFFFFFFu;
+__device__ __forceinline__ void occ_push(uint32_t* occ, uint32_t slot) {
+#pragma unroll
+  for (int k = kOccK - 1; k > 0; k--) occ[k] = occ[k - 1];
+  occ[0] = slot;
+}
+
 // calculateDistance (flyscene.cpp:444-478) against a wave-uniform triangle record, for the lanes of
 // `act`. CLOSEST: update (t, rank, slot) if 0 <= t < best (rank breaks ties as the reference's order
 // does). ANY: any valid t >= 0 (shadow(), flyscene.cpp:519).
 template <bool ANY, bool STATS = false>
 __device__ __forceinline__ void test_tri(const DevScene& P, const TriRec64& tr, uint32_t slot, const Ray& r,
                                          uint64_t act, Hit& h, bool& found, uint32_t* cnt = nullptr,
-                                         uint64_t entry = ~0ull, bool desc = false) {
+                                         uint64_t entry = ~0ull, bool desc = false, uint32_t* occ = nullptr) {
   const f3 n{tr.nx, tr.ny, tr.nz};
   const float dn = dot(n, r.d);                 // facenormal.dot(dir)
   const float orth = tr.dist - dot(r.o, n);     // distancePlane - origin.dot(facenormal)
@@ -399,6 +409,9 @@ __device__ __forceinline__ void test_tri(const DevScene& P, const TriRec64& tr, 
   const bool acc = lane_in(accept_candidate(P, tr, slot, e0, e2, a0, a1, a2, p, r, cand));
   if (STATS) cnt[ST_WACCX] += (ballot(acc) & ~entry) != 0;
   if (ANY) {
+    // occluder cache (calc_color, memory-lights kernels only; null everywhere else): the slot at which some
+    // lane first became blocked goes to the front of the wave's last kOccK occluders
+    if (occ != nullptr && ballot(acc && !found) != 0) occ_push(occ, slot);
     found = found | acc;
   } else {
     h.t = acc ? t : h.t;
@@ -431,7 +444,7 @@ constexpr int order_bit() {
 }
 template <bool ANY, bool STATS, bool STACK_LDS, int OCT = -1>
 __device__ __forceinline__ void traverse(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
-                                         uint32_t* lds_stack, uint32_t* cnt) {
+                                         uint32_t* lds_stack, uint32_t* cnt, uint32_t* occ = nullptr) {
   if (P.n_nodes == 0) return;
   uint32_t stackv = 0;     // lane k holds stack entry k (VGPR stack)
   int sp = 0;              // wave-uniform stack depth (SGPR)
@@ -525,7 +538,7 @@ __device__ __forceinline__ void traverse(const DevScene& P, const Ray& r, bool a
       }
       for (uint32_t k = 0; k < count; k++) {
         const TriRec64 tr = sload_tri(P.tris, first + k);
-        test_tri<ANY, STATS>(P, tr, first + k, r, act, h, found, cnt, STATS ? ballot(want) : ~0ull, desc);
+        test_tri<ANY, STATS>(P, tr, first + k, r, act, h, found, cnt, STATS ? ballot(want) : ~0ull, desc, occ);
       }
       if (ANY) {
         active = active & !found;
@@ -588,7 +601,7 @@ __device__ __forceinline__ void lds_push(uint32_t* slot, uint32_t v) {
 // push only when both children are needed.
 template <bool ANY, int OCT>
 __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
-                                                   uint32_t* lds_stack, uint32_t node, int sp) {
+                                                   uint32_t* lds_stack, uint32_t node, int sp, uint32_t* occ = nullptr) {
   // lanes still tracing: used by the any-hit triangle tests only (a closest-hit lane without a ray
   // carries t_best = -1, which no candidate t >= -0 passes, so its triangle tests need no mask)
   uint64_t act = ANY ? ballot(active) : ~0ull;
@@ -683,7 +696,7 @@ __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray&
       }
       for (uint32_t k = 0; k < count; k++) {
         const TriRec64 tr = sload_tri(P.tris, first + k);
-        test_tri<ANY>(P, tr, first + k, r, act, h, found);
+        test_tri<ANY>(P, tr, first + k, r, act, h, found, nullptr, ~0ull, false, occ);
       }
       if (ANY) {
         active = active & !found;
@@ -702,9 +715,9 @@ __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray&
 
 template <bool ANY, int OCT>
 __device__ __forceinline__ void traverse_fast(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
-                                              uint32_t* lds_stack) {
+                                              uint32_t* lds_stack, uint32_t* occ = nullptr) {
   if (P.n_nodes == 0) return;
-  traverse_fast_from<ANY, OCT>(P, r, active, h, found, lds_stack, P.root, 0);
+  traverse_fast_from<ANY, OCT>(P, r, active, h, found, lds_stack, P.root, 0, occ);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -930,11 +943,11 @@ __device__ __forceinline__ void traverse_lane(const DevScene& P, const Ray& r, b
 
 template <bool ANY, bool STATS, int TRAV>
 __device__ __forceinline__ void trace(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
-                                      WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt) {
+                                      WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt, uint32_t* occ = nullptr) {
   if constexpr (TRAV == TRAV_W4) traverse4<ANY, STATS>(P, r, active, h, found, L.stack[wv], L.mask[STATS ? wv : 0], cnt);
   else if constexpr (TRAV == TRAV_LANE) traverse_lane<ANY, STATS>(P, r, active, h, found, cnt);
-  else if constexpr (!STATS && TRAV == TRAV_B2_LDS) traverse_fast<ANY, -1>(P, r, active, h, found, L.stack[wv]);
-  else traverse<ANY, STATS, TRAV == TRAV_B2_LDS>(P, r, active, h, found, L.stack[wv], cnt);
+  else if constexpr (!STATS && TRAV == TRAV_B2_LDS) traverse_fast<ANY, -1>(P, r, active, h, found, L.stack[wv], occ);
+  else traverse<ANY, STATS, TRAV == TRAV_B2_LDS>(P, r, active, h, found, L.stack[wv], cnt, occ);
 }
 
 // Packet traversal specialised by the wave's direction octant when every active ray shares it (coherent
@@ -1037,8 +1050,8 @@ __device__ __forceinline__ void trace_closest_oct(const DevScene& P, const Ray& 
 // incoherent FULL-mode packets (the generic loop)
 template <bool ANY, bool STATS, int TRAV>
 __device__ __forceinline__ void trace_full_ray(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
-                                               WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt) {
-  trace<ANY, STATS, TRAV>(P, r, active, h, found, L, wv, cnt);
+                                               WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt, uint32_t* occ = nullptr) {
+  trace<ANY, STATS, TRAV>(P, r, active, h, found, L, wv, cnt, occ);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1100,6 +1113,23 @@ __device__ __forceinline__ Light frame_light(int l) {
   return r;
 }
 
+// Light l of a light set (rt_light_set, FrameParams::light_set): the set's device array, in calculateColor's
+// order, read through the constant address space -- base and l are wave-uniform, so these are scalar loads
+// (one fetch per wave into SGPRs, as frame_light's) and nothing is ever written there
+__device__ __forceinline__ Light set_light(const FrameParams& P, int l) {
+  typedef const __attribute__((address_space(4))) Light* CLight;
+  const uint64_t b = (uint64_t)P.light_set;
+  const uint64_t bs = ((uint64_t)uniform((uint32_t)(b >> 32)) << 32) | (uint32_t)uniform((uint32_t)b);
+  const CLight q = (CLight)bs + uniform((uint32_t)l);
+  Light r;
+  for (int k = 0; k < 3; k++) {
+    r.p[k] = q->p[k];
+    r.c[k] = q->c[k];
+  }
+  r.kind = q->kind;
+  return r;
+}
+
 // calculateColor's light direction (flyscene.cpp:607-611): point light -(P - pos).normalized(), or a
 // directional light's stored vector as is
 __device__ __forceinline__ f3 light_dir(f3 p, const Light& l) {
@@ -1130,12 +1160,26 @@ __device__ __forceinline__ float clamp01(float x) { return smax(smin(x, 1.0f), 0
 
 // calculateColor (flyscene.cpp:603-614). SHADOWS: per light, a wave-packet any-hit traversal from
 // P + 0.003 L (box predicate from P) decides whether the light contributes (calcSingleColor :543).
-template <bool SHADOWS, bool STATS, int TRAV, bool OCTSH = false, bool SPLIT = false>
+// LSRC: where light l comes from -- LS_KERNARG: frame_light(l), every kernel of rt_render's path; LS_MEMORY /
+// LS_MEMORY_CACHED: set_light(P, l), the light-set instantiations of the generic kernels. Same arithmetic and
+// summation order either way, hence the same bits for the same lights.
+// LS_MEMORY_CACHED adds the wave-level occluder cache to the shadow packets. shadow(P, L) is true iff any triangle
+// passes test_tri<true>; which one is found first never matters. The lights of a soft (spherical) light lie close
+// together, so the triangle that blocked light l for some lanes very often blocks light l + 1 for the same lanes.
+// The walk reports the slots at which lanes first became blocked (test_tri's occ); before the walk of the next
+// light the wave runs test_tri<true> -- the leaves' own test: plane, edges, normal check, box predicate and
+// certificates -- on those kOccK records for the lanes not yet blocked, walks only for the lanes that remain, and
+// skips the walk when none do. A lane the pre-test blocks is one a leaf visit would have blocked: bit-identical.
+// The cache lives in this call, so it starts empty at each hit level.
+template <bool SHADOWS, bool STATS, int TRAV, bool OCTSH = false, bool SPLIT = false, int LSRC = LS_KERNARG>
 __device__ __forceinline__ f3 calc_color(const FrameParams& P, MatState& st, const HitInfo& hi, f3 o, bool lane_hit,
                                          WaveLds<TRAV, STATS>* lds, int wv, uint32_t* cnt) {
   f3 sum{0.0f, 0.0f, 0.0f};
+  uint32_t occ[kOccK];
+#pragma unroll
+  for (int k = 0; k < kOccK; k++) occ[k] = kOccNone;
   for (int l = 0; l < P.n_lights; l++) {
-    const Light lt = frame_light(l);
+    const Light lt = LSRC == LS_KERNARG ? frame_light(l) : set_light(P, l);
     const f3 L = light_dir(hi.p, lt);
     bool blocked = false;
     if (SHADOWS) {
@@ -1146,7 +1190,22 @@ __device__ __forceinline__ f3 calc_color(const FrameParams& P, MatState& st, con
       setup_cull(sr, P.sc.static_pad);
       Hit hh{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
       if (STATS && lane_hit) cnt[ST_TOTAL]++;
-      if (OCTSH)
+      if constexpr (LSRC == LS_MEMORY_CACHED) {
+#pragma unroll
+        for (int k = 0; k < kOccK; k++) {
+          const uint32_t slot = uniform(occ[k]);
+          const uint64_t rem = ballot(lane_hit && !blocked);
+          if (slot == kOccNone || rem == 0) continue;
+          const TriRec64 tr = sload_tri(P.sc.tris, slot);
+          if (STATS) {  // a record fetched once per wave and tested by the remaining lanes, as in a leaf
+            cnt[ST_WTRI]++;
+            if (lane_hit && !blocked) cnt[ST_TRI]++;
+          }
+          test_tri<true>(P.sc, tr, slot, sr, rem, hh, blocked);
+        }
+        const bool remain = lane_hit && !blocked;
+        if (ballot(remain) != 0) trace_full_ray<true, STATS, TRAV>(P.sc, sr, remain, hh, blocked, *lds, wv, cnt, occ);
+      } else if (OCTSH)
         trace_oct<true, STATS, TRAV, false, SPLIT>(P.sc, sr, lane_hit, hh, blocked, *lds, wv, cnt);
       else trace_full_ray<true, STATS, TRAV>(P.sc, sr, lane_hit, hh, blocked, *lds, wv, cnt);
     }
@@ -1666,7 +1725,9 @@ void k_render_full(FrameParams P) {
 // reflection returned black: a miss below depth 0, or depth == max_depth). D = 0 returns black for
 // every pixel without tracing (traceRay :318-320). Same expressions and order as k_render_full for
 // D = 2, hence the same bits (tested); this kernel serves the other depths.
-template <bool STATS, bool HITS>
+// LSRC (calc_color): LS_KERNARG for rt_render's frames; the light-set frames beyond 32 lights instantiate
+// LS_MEMORY_CACHED (LS_MEMORY: the same without the occluder cache, VB_NO_OCCLUDER_CACHE).
+template <bool STATS, bool HITS, int LSRC = LS_KERNARG>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEuSmall)))
 void k_render_depth(FrameParams P) {
   __shared__ WaveLds<TRAV_B2_LDS, STATS> lds;
@@ -1707,8 +1768,8 @@ void k_render_depth(FrameParams P) {
       h0 = h;
       face0 = hit ? hi.face : 0xFFFFFFFFu;
     }
-    const f3 dc = P.shadows ? calc_color<true, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, c.slot, cnt)
-                            : calc_color<false, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, c.slot, cnt);
+    const f3 dc = P.shadows ? calc_color<true, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, hit, &lds, c.slot, cnt)
+                            : calc_color<false, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, hit, &lds, c.slot, cnt);
     if (hit) {
       direct[d] = dc;
       levels = d + 1;
@@ -1847,7 +1908,7 @@ void k_rays_color(FrameParams P, RayParams R) {
 // h0 / face0 the first hit (face0 = ~0: a miss). A copy, statement for statement, and not a function both kernels
 // share: with the loop moved into a function k_render_depth's scratch size and spill counts changed (make asm), and
 // the frame kernels stay as they are. Keep the two in step.
-template <bool STATS>
+template <bool STATS, int LSRC = LS_KERNARG>
 __device__ __forceinline__ f3 trace_depth(const FrameParams& P, Ray cur, bool active, WaveLds<TRAV_B2_LDS, STATS>& lds,
                                           int slot, uint32_t* cnt, Hit& h0, uint32_t& face0) {
   MatState st = load_mat(P.defmat);
@@ -1880,8 +1941,8 @@ __device__ __forceinline__ f3 trace_depth(const FrameParams& P, Ray cur, bool ac
       h0 = h;
       face0 = hit ? hi.face : 0xFFFFFFFFu;
     }
-    const f3 dc = P.shadows ? calc_color<true, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, slot, cnt)
-                            : calc_color<false, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, slot, cnt);
+    const f3 dc = P.shadows ? calc_color<true, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, hit, &lds, slot, cnt)
+                            : calc_color<false, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, hit, &lds, slot, cnt);
     if (hit) {
       direct[d] = dc;
       levels = d + 1;
@@ -1909,7 +1970,7 @@ __device__ __forceinline__ f3 trace_depth(const FrameParams& P, Ray cur, bool ac
 
 // traceRay(o, d, 0) at any recursion limit, with or without shadow rays (P.max_depth, P.shadows), for a list of
 // rays (rt_trace_stream_color): the level loop (trace_depth) under the list packets' addressing
-template <bool STATS>
+template <bool STATS, int LSRC = LS_KERNARG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEu)))
 void k_rays_depth(FrameParams P, RayParams R) {
   __shared__ WaveLds<TRAV_B2_LDS, STATS> lds;
@@ -1928,7 +1989,7 @@ void k_rays_depth(FrameParams P, RayParams R) {
   if (STATS && active) { cnt[ST_RAYS]++; cnt[ST_TOTAL]++; }
   Hit h;
   uint32_t face0;
-  const f3 col = trace_depth<STATS>(P, r, active, lds, wv, cnt, h, face0);
+  const f3 col = trace_depth<STATS, LSRC>(P, r, active, lds, wv, cnt, h, face0);
   if (STATS) flush_stats(P, cnt, lane);
   if (!active) return;
   R.rgb[3 * (size_t)i + 0] = col.x;

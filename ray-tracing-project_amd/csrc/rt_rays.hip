@@ -181,13 +181,18 @@ int enqueue_rays(rt_scene* s, int query, int flags, RayParams R, const rt_light*
 // ---- rt_trace_stream_color: traceRay at any depth and mode ----
 
 // the in-order (or level-0 reordered) list kernel k_rays_depth; P carries mode, depth and lights
-int enqueue_rays_depth(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st) {
+int enqueue_rays_depth(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st, int lsrc) {
   const bool stats = (flags & RT_RAYS_STATS) != 0, reorder = (flags & RT_RAYS_REORDER) != 0;
   int rc;
   if (reorder && (rc = begin_reorder(s, R, st))) return rc;
   if (stats && (rc = begin_stats(s, P, st))) return rc;
   const int grid = (R.n + 255) / 256;
-  with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  if (lsrc == LS_MEMORY_CACHED)
+    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value, LS_MEMORY_CACHED>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  else if (lsrc == LS_MEMORY)
+    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value, LS_MEMORY>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  else
+    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
   HIPCHECK(hipGetLastError());
   if (R.perm) {
     HIPCHECK(hipEventRecord((hipEvent_t)s->rays.ev, st));
@@ -238,7 +243,7 @@ int ensure_wavefront(rt_scene* s, size_t n, int D) {
 
 // RT_RAYS_WAVEFRONT: the stage kernels of every level, the regroups between them, the resolve pass -- all on st,
 // launched for the upper bound n (the live counts stay on the device)
-int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st) {
+int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipStream_t st, int lsrc) {
   const int n = R.n, D = P.max_depth;
   const bool stats = (flags & RT_RAYS_STATS) != 0, reorder = (flags & RT_RAYS_REORDER) != 0;
   const bool sorting = reorder && n > 64;  // up to 64 rays are one packet in any order
@@ -291,18 +296,29 @@ int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipSt
     W.list = in;
     if (fused) {
       W.mark = last ? nullptr : W.s.key_a;
-      with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, true, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
+      if (lsrc != LS_KERNARG)
+        with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, true, ST.value, LS_MEMORY>), grid, block, 0, st, P, W); }, d == 0, stats);
+      else
+        with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, true, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
       HIPCHECK(hipGetLastError());
       if (!last && (rc = regroup(in))) return rc;
       continue;
     }
     W.mark = W.s.key_a;
-    with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, false, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
+    if (lsrc != LS_KERNARG)
+      with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, false, ST.value, LS_MEMORY>), grid, block, 0, st, P, W); }, d == 0, stats);
+    else
+      with_bools([&](auto FI, auto ST) { hipLaunchKernelGGL((k_wf_closest<FI.value, false, ST.value>), grid, block, 0, st, P, W); }, d == 0, stats);
     HIPCHECK(hipGetLastError());
     if ((rc = regroup(in))) return rc;  // the hits, for the shade stage
     W.list = in;
     W.mark = (sorting && !last) ? W.s.key_a : nullptr;  // without a sort the hit list is the next level's list
-    with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value>), grid, block, 0, st, P, W); }, stats);
+    if (lsrc == LS_MEMORY_CACHED)
+      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value, LS_MEMORY_CACHED>), grid, block, 0, st, P, W); }, stats);
+    else if (lsrc == LS_MEMORY)
+      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value, LS_MEMORY>), grid, block, 0, st, P, W); }, stats);
+    else
+      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value>), grid, block, 0, st, P, W); }, stats);
     HIPCHECK(hipGetLastError());
     if (W.mark && (rc = regroup(in))) return rc;
   }
@@ -467,24 +483,25 @@ extern "C" int rt_trace_stream(rt_scene* s, int32_t query, int32_t flags, const 
   return check_prefetch_word(s);
 }
 
-extern "C" int rt_trace_stream_color(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light* lights,
-                                     int32_t n_lights, int32_t mode, int32_t max_depth, void* hip_stream) {
+// rt_trace_stream_color (lights / n_lights from host memory, ls null) and rt_trace_stream_lit (the light set ls)
+static int trace_stream_color(const char* who, rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light* lights,
+                              int32_t n_lights, const rt_light_set* ls, int32_t mode, int32_t max_depth, void* hip_stream) {
   // argument checks that need no device come first
   if (!s) { set_error("null scene"); return RT_ERR_INVALID; }
-  if (mode != RT_MODE_PRIMARY && mode != RT_MODE_FULL) { set_error("rt_trace_stream_color: bad mode %d", mode); return RT_ERR_INVALID; }
+  if (mode != RT_MODE_PRIMARY && mode != RT_MODE_FULL) { set_error("%s: bad mode %d", who, mode); return RT_ERR_INVALID; }
   if (max_depth < 0 || max_depth > RT_MAX_TRACE_DEPTH) {
-    set_error("rt_trace_stream_color: max_depth %d outside 0..%d", max_depth, RT_MAX_TRACE_DEPTH);
+    set_error("%s: max_depth %d outside 0..%d", who, max_depth, RT_MAX_TRACE_DEPTH);
     return RT_ERR_INVALID;
   }
   if (flags & ~(RT_RAYS_REORDER | RT_RAYS_STATS | RT_RAYS_WAVEFRONT)) {
-    set_error("rt_trace_stream_color: bad flags %d", flags);
+    set_error("%s: bad flags %d", who, flags);
     return RT_ERR_INVALID;
   }
-  if (!rays || rays->n < 0) { set_error("rt_trace_stream_color: invalid arguments"); return RT_ERR_INVALID; }
+  if (!rays || rays->n < 0) { set_error("%s: invalid arguments", who); return RT_ERR_INVALID; }
   const int32_t n = rays->n;
   if (n > 0) {
-    if (!rays->a3 || !rays->b3 || check_lights(lights, n_lights)) { set_error("rt_trace_stream_color: invalid arguments"); return RT_ERR_INVALID; }
-    if (!rays->rgb3) { set_error("rt_trace_stream_color: needs rgb3"); return RT_ERR_INVALID; }
+    if (!rays->a3 || !rays->b3 || check_lights(lights, n_lights)) { set_error("%s: invalid arguments", who); return RT_ERR_INVALID; }
+    if (!rays->rgb3) { set_error("%s: needs rgb3", who); return RT_ERR_INVALID; }
   }
   int rc = check_device_scene(s);
   if (rc) return rc;
@@ -495,27 +512,44 @@ extern "C" int rt_trace_stream_color(rt_scene* s, int32_t flags, const rt_ray_st
   R.face = rays->face, R.t = rays->t, R.rgb = rays->rgb3;
   const struct { const void* p; const char* what; } ptrs[] = {{R.o, "a3"}, {R.d, "b3"}, {R.face, "face"}, {R.t, "t"}, {R.rgb, "rgb3"}};
   for (const auto& q : ptrs)
-    if ((rc = check_device_pointer(s, q.p, "rt_trace_stream_color", q.what))) return rc;
+    if ((rc = check_device_pointer(s, q.p, who, q.what))) return rc;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)s->stream;
   const int depth = max_depth > 0 ? max_depth : (mode == RT_MODE_FULL ? 2 : 1);
   const bool wavefront = (flags & RT_RAYS_WAVEFRONT) != 0;
-  if (mode == RT_MODE_FULL && depth == 2 && !wavefront) {  // the existing RT_RAYS_COLOR path, same kernel
-    rc = enqueue_rays(s, Q_COLOR, flags, R, lights, n_lights, st);
+  // a light set: in the kernel arguments when it fits (then exactly the lights / n_lights call), else devices[0]'s
+  // copy in device memory, which only the generic list kernels read
+  FrameParams P;
+  fill_scene_params(s, P);
+  int lsrc = LS_KERNARG;
+  if (ls) lsrc = fill_light_set(P, ls, 0);
+  else fill_lights(P, lights, n_lights);
+  if (mode == RT_MODE_FULL && depth == 2 && !wavefront && lsrc == LS_KERNARG) {  // the existing RT_RAYS_COLOR path, same kernel
+    rc = ls ? enqueue_rays(s, Q_COLOR, flags, R, ls->host.data(), (int32_t)ls->host.size(), st)
+            : enqueue_rays(s, Q_COLOR, flags, R, lights, n_lights, st);
   } else {
-    FrameParams P;
-    fill_scene_params(s, P);
-    fill_lights(P, lights, n_lights);
     P.mode = mode, P.max_depth = depth, P.shadows = mode == RT_MODE_FULL ? 1 : 0;
     if (pick_trav(kernel_variant(), P.sc.n_nodes4 > 0) == TRAV_W4) {
-      set_error("rt_trace_stream_color: only the binary-tree kernels trace this mode / depth / flag, not kernel variant %d", kernel_variant());
+      set_error("%s: only the binary-tree kernels trace this mode / depth / flag, not kernel variant %d", who, kernel_variant());
       return RT_ERR_UNSUPPORTED;
     }
-    rc = wavefront ? enqueue_wavefront(s, flags, R, P, st) : enqueue_rays_depth(s, flags, R, P, st);
+    rc = wavefront ? enqueue_wavefront(s, flags, R, P, st, lsrc) : enqueue_rays_depth(s, flags, R, P, st, lsrc);
   }
   if (rc) return rc;
   if (hip_stream) return RT_OK;
   HIPCHECK(hipStreamSynchronize(st));
   return check_prefetch_word(s);
+}
+
+extern "C" int rt_trace_stream_color(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light* lights,
+                                     int32_t n_lights, int32_t mode, int32_t max_depth, void* hip_stream) {
+  return trace_stream_color("rt_trace_stream_color", s, flags, rays, lights, n_lights, nullptr, mode, max_depth, hip_stream);
+}
+
+extern "C" int rt_trace_stream_lit(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light_set* ls, int32_t mode,
+                                   int32_t max_depth, void* hip_stream) {
+  if (s && !ls) { set_error("rt_trace_stream_lit: null light set"); return RT_ERR_INVALID; }
+  if (s && ls->scene != s) { set_error("rt_trace_stream_lit: the light set belongs to another scene"); return RT_ERR_INVALID; }
+  return trace_stream_color("rt_trace_stream_lit", s, flags, rays, nullptr, 0, ls, mode, max_depth, hip_stream);
 }
 
 extern "C" int rt_debug_ray_levels(rt_scene* s, int32_t capacity, int64_t* out2, int32_t* n_levels) {

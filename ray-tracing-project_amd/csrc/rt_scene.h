@@ -129,6 +129,15 @@ namespace rt {
 struct EnqueueWorker;  // rt_device.hip: a host thread that queues one replica's share of each frame
 }
 
+// A light set (rt_api.h): the lights in calculateColor's order (points, then directionals; kinds normalised), on the
+// host and -- unless the scene is host-only -- as one rt::Light array per device of the scene (dev[k]: replica k's,
+// k = 0 the scene itself). Immutable after rt_light_set_create; owned by its scene (rt_scene::light_sets).
+struct rt_light_set {
+  rt_scene* scene = nullptr;
+  std::vector<rt_light> host;
+  std::vector<rt::Light*> dev;
+};
+
 struct rt_scene {
   rt_scene_opts opts;
   // the host scene; shared with the scene's device replicas (one HostScene per rt_scene_create)
@@ -265,6 +274,7 @@ struct rt_scene {
   float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
   bool ray_bounds_valid = false;
   bool pending = false;
+  std::vector<rt_light_set*> light_sets;  // the scene's live light sets (freed with the scene; rt_device.hip)
 };
 
 namespace rt {

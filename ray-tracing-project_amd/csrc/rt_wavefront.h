@@ -133,7 +133,9 @@ __device__ __forceinline__ void wf_finish_level(const FrameParams& P, const WfPa
 // octant-specialised walk of the in-order loop's level 0, the first hit's outputs, the default material); an
 // instantiation of its own, so that a level's kernel holds one traversal. FUSED: PRIMARY mode or no lights -- the
 // shading is done here and the hits are the next level's rays.
-template <bool FIRST, bool FUSED, bool STATS>
+// LSRC: LS_KERNARG, or LS_MEMORY for a light set read from device memory (rt_trace_stream_lit): the fused shading
+// has no shadow packets and hence no occluder cache, the shade stage's key reads the set's first light.
+template <bool FIRST, bool FUSED, bool STATS, int LSRC = LS_KERNARG>
 __global__ __launch_bounds__(256) void k_wf_closest(FrameParams P, WfParams W) {
   __shared__ WaveLds<TRAV_B2_LDS, STATS> lds;
   WfLane c;
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(256) void k_wf_closest(FrameParams P, WfParams W) {
   if (c.lane == 0 && nh) atomicAdd(W.counts + d + 1, nh);
   if (FUSED) {
     MatState st = FIRST ? load_mat(P.defmat) : wf_load_mat(W.s, i);
-    const f3 dc = calc_color<false, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, hit, &lds, c.wv, cnt);
+    const f3 dc = calc_color<false, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, hit, &lds, c.wv, cnt);
     if (hit) wf_finish_level(P, W, c, cur, hi, st, dc);
     else if (c.active && W.mark) W.mark[c.base + c.lane] = W.bounds ? kWfDeadKey : 0u;
   } else {
@@ -190,7 +192,7 @@ __global__ __launch_bounds__(256) void k_wf_closest(FrameParams P, WfParams W) {
     }
     if (c.active) {  // the shade stage's key: the hit point and the direction to calculateColor's first light
       uint32_t m = W.bounds ? kWfDeadKey : 0u;
-      if (hit) m = W.bounds ? wf_key(W, hi.p, light_dir(hi.p, frame_light(0))) : 1u;
+      if (hit) m = W.bounds ? wf_key(W, hi.p, light_dir(hi.p, LSRC == LS_KERNARG ? frame_light(0) : set_light(P, 0))) : 1u;
       W.mark[c.base + c.lane] = m;
     }
   }
@@ -198,7 +200,8 @@ __global__ __launch_bounds__(256) void k_wf_closest(FrameParams P, WfParams W) {
 }
 
 // Shade stage of level W.level (FULL with lights) over the hit list of counts[level + 1] entries
-template <bool STATS>
+// LSRC: calc_color's light source (LS_MEMORY_CACHED / LS_MEMORY for a light set read from device memory)
+template <bool STATS, int LSRC = LS_KERNARG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEu)))
 void k_wf_shade(FrameParams P, WfParams W) {
   __shared__ WaveLds<TRAV_B2_LDS, STATS> lds;
@@ -216,7 +219,7 @@ void k_wf_shade(FrameParams P, WfParams W) {
   hi.mat = W.s.hmat[i];
   hi.face = W.s.hface[i];
   MatState st = wf_load_mat(W.s, i);
-  const f3 dc = calc_color<true, STATS, TRAV_B2_LDS>(P, st, hi, cur.o, c.active, &lds, c.wv, cnt);
+  const f3 dc = calc_color<true, STATS, TRAV_B2_LDS, false, false, LSRC>(P, st, hi, cur.o, c.active, &lds, c.wv, cnt);
   if (c.active) wf_finish_level(P, W, c, cur, hi, st, dc);
   if (STATS) flush_stats(P, cnt, c.lane);
 }

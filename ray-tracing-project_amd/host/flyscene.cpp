@@ -81,6 +81,24 @@ void Flyscene::initialize(int width, int height, const std::string& obj_path, in
   if (!cache_path.empty() && rt_scene_save(scene_, cache_path.c_str()) != RT_OK) fprintf(stderr, "%s\n", rt_last_error());
 }
 
+void Flyscene::sphericalLight(std::pair<Vec3, Vec3> light, float radius, int nLightpoints) {
+  if (nLightpoints <= 0) return;
+  if (!rng_seeded_) {
+    rt_rand_seed(&rng_, 1);
+    rng_seeded_ = true;
+  }
+  const rt_light centre{{light.first.x, light.first.y, light.first.z}, {light.second.x, light.second.y, light.second.z},
+                        RT_LIGHT_POINT};
+  std::vector<rt_light> out((size_t)nLightpoints + 1);  // the jittered lights, then the centre (not pushed here)
+  if (rt_lights_spherical(&centre, radius, nLightpoints, &rng_, out.data()) < 0) {
+    fprintf(stderr, "%s\n", rt_last_error());
+    return;
+  }
+  for (int i = 0; i < nLightpoints; i++)
+    lights.push_back({Vec3{out[i].position[0], out[i].position[1], out[i].position[2]},
+                      Vec3{out[i].color[0], out[i].color[1], out[i].color[2]}});
+}
+
 double Flyscene::raytraceScene(int width, int height) {
   if (!scene_) { fprintf(stderr, "raytraceScene: no scene\n"); return -1.0; }
   if (width == 0 || height == 0) {
@@ -100,7 +118,17 @@ double Flyscene::raytraceScene(int width, int height) {
   const auto t0 = std::chrono::steady_clock::now();
   // render, then the 8-bit frame (3 B/px over PCIe); the float frame only when some value falls outside
   // the PPM's 0..255 (NaN / negative colours), where writePPMImage's own numbers are reproduced from it
-  if (rt_render(scene_, &cam, ls.data(), (int32_t)ls.size(), &fr, nullptr, &st) != RT_OK) {
+  // up to RT_MAX_LIGHTS lights travel with the call; more (a soft light) go through a light set
+  int rrc;
+  if (ls.size() > (size_t)RT_MAX_LIGHTS) {
+    rt_light_set* set = nullptr;
+    rrc = rt_light_set_create(scene_, ls.data(), (int32_t)ls.size(), &set);
+    if (rrc == RT_OK) rrc = rt_render_lit(scene_, &cam, set, &fr, nullptr, &st);
+    rt_light_set_destroy(set);
+  } else {
+    rrc = rt_render(scene_, &cam, ls.data(), (int32_t)ls.size(), &fr, nullptr, &st);
+  }
+  if (rrc != RT_OK) {
     fprintf(stderr, "%s\n", rt_last_error());
     return -1.0;
   }

@@ -1,7 +1,8 @@
 // flyscene.hpp -- GL-free mirror of the reference's render-to-image entry point
 // (src/flyscene.hpp:22-186). It keeps the reference's call shape -- initialize(w, h), getCamera(),
 // the public `lights` vector and raytraceScene(w, h) writing result.ppm -- and replaces the
-// 20-thread CPU traceRay loop (flyscene.cpp:250-314) with one rt_render() call on the GPU.
+// 20-thread CPU traceRay loop (flyscene.cpp:250-314) with one rt_render() call on the GPU (rt_render_lit through a
+// light set once `lights` holds more than RT_MAX_LIGHTS entries, e.g. after sphericalLight).
 // Only the ray-tracing state is mirrored; the OpenGL preview, debug rays and stdin light prompts
 // are out of scope.
 #pragma once
@@ -53,6 +54,12 @@ class Flyscene {
   // Returns the device kernel time in milliseconds (negative on failure; message on stderr).
   double raytraceScene(int width = 0, int height = 0);
 
+  // flyscene.cpp:529-538: pushes nLightpoints point lights jittered within `radius` of light.first, each with
+  // colour light.second / (nLightpoints + 1), onto `lights` (rt_lights_spherical; the jitter continues this
+  // scene's rand() sequence, seed 1 = a fresh reference process). As in the reference the centre light is the
+  // caller's to add: addLight('s') then pushes light with its colour divided by nLightpoints + 1 (:235-239).
+  void sphericalLight(std::pair<Vec3, Vec3> light, float radius, int nLightpoints);
+
   Flycamera* getCamera() { return &flycamera; }
   // what initialize() built (rt_scene_get_info of the scene) and how long it took (OBJ load + scene setup, or
   // the cache load), for the CLI's report; false before a successful initialize()
@@ -82,6 +89,8 @@ class Flyscene {
   rt_mesh* mesh_ = nullptr;
   rt_scene* scene_ = nullptr;
   double setup_s_ = 0.0, build_s_ = 0.0;
+  rt_rand_state rng_;       // the reference's unseeded rand() (sphericalLight)
+  bool rng_seeded_ = false;
 };
 
 }  // namespace fly

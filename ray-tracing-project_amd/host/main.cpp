@@ -2,6 +2,9 @@
 // initialize a Flyscene, optionally move the Flycamera, ray trace, write the PPM.
 //   rt_render_cli <scene.obj> [W H] [--primary] [--dz N] [--out result.ppm] [--device D] [--cache file]
 //                 [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...]
+//                 [--spherical-light X Y Z RADIUS N]
+// --spherical-light: the default light is replaced by a white spherical light at (X, Y, Z): N point lights jittered
+// within RADIUS plus the centre, as the reference's addLight('s') builds it (flyscene.cpp:212-239)
 // The scene is built as the library's default (rt_scene_opts_default: the SBVH and the reference box partition
 // on the device, the configuration the benchmarks measure); --host-build builds the same tree and boxes on the
 // host instead, --lbvh the device LBVH. The scene setup time and the builders that ran are printed.
@@ -18,7 +21,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s scene.obj [W H] [--primary] [--dz N] [--out file.ppm] [--device D] [--cache file] [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...]\n",
+    fprintf(stderr, "usage: %s scene.obj [W H] [--primary] [--dz N] [--out file.ppm] [--device D] [--cache file] [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...] [--spherical-light X Y Z RADIUS N]\n",
             argv[0]);
     return 2;
   }
@@ -28,6 +31,9 @@ int main(int argc, char** argv) {
   float dz = 0.0f;
   int pos = 0;
   std::vector<int> devices;  // empty: one device; {-1}: every visible device
+  bool soft = false;
+  float soft_pos[3] = {0, 0, 0}, soft_radius = 0.0f;
+  int soft_n = 0;
   for (int i = 2; i < argc; i++) {
     if (!strcmp(argv[i], "--primary")) mode = RT_MODE_PRIMARY;
     else if (!strcmp(argv[i], "--box-colors")) mode = RT_MODE_BOX_COLORS;
@@ -38,6 +44,12 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--lbvh")) builder = RT_BUILDER_LBVH_GPU;
     else if (!strcmp(argv[i], "--host-build")) { builder = RT_BUILDER_SBVH; box_builder = RT_BOXES_HOST; }
     else if (!strcmp(argv[i], "--gpu-boxes")) box_builder = RT_BOXES_GPU;
+    else if (!strcmp(argv[i], "--spherical-light") && i + 5 < argc) {
+      soft = true;
+      for (int k = 0; k < 3; k++) soft_pos[k] = (float)atof(argv[++i]);
+      soft_radius = (float)atof(argv[++i]);
+      soft_n = std::max(0, atoi(argv[++i]));
+    }
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
       const std::string list = argv[++i];
       if (list == "all") {
@@ -66,6 +78,15 @@ int main(int argc, char** argv) {
            scene.setupSeconds(), scene.buildSeconds(), info.n_faces,
            info.builder >= 0 && info.builder <= 5 ? names[info.builder] : "?", info.box_builder == RT_BOXES_GPU ? "gpu" : "host",
            info.n_devices);
+  }
+  if (soft) {  // addLight('s'): the jittered lights, then the centre with its colour divided by N + 1
+    scene.lights.clear();
+    std::pair<fly::Vec3, fly::Vec3> light{fly::Vec3{soft_pos[0], soft_pos[1], soft_pos[2]}, fly::Vec3{1.0f, 1.0f, 1.0f}};
+    scene.sphericalLight(light, soft_radius, soft_n);
+    const float div = (float)(soft_n + 1);
+    light.second = fly::Vec3{light.second.x / div, light.second.y / div, light.second.z / div};
+    scene.lights.push_back(light);
+    printf("spherical light: %zu point lights\n", scene.lights.size());
   }
   scene.mode = mode;
   scene.output = out;

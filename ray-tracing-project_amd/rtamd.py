@@ -44,7 +44,13 @@ EXPORTS = [
     "rt_synchronize_devices", "rt_debug_lpt_stats", "rt_debug_wave_stats", "rt_debug_frame_plan",
     "rt_trace_stream", "rt_rays_camera", "rt_scene_ray_bounds", "rt_debug_ray_keys", "rt_debug_ray_order",
     "rt_trace_stream_color", "rt_debug_ray_levels",
+    "rt_light_set_create", "rt_light_set_destroy", "rt_light_set_get", "rt_render_lit", "rt_render_lit_async",
+    "rt_trace_stream_lit",
 ]
+RT_MAX_LIGHTS = 32
+RT_MAX_LIGHT_SET = 65536
+VARIANT_MEM_LIGHTS = 8388608         # light sets read from device memory at any count (tests, A/B)
+VARIANT_NO_OCCLUDER_CACHE = 16777216  # the memory-lights kernels without the occluder cache (tests, A/B)
 RT_MAX_DEVICES = 16
 RT_DEVICES_ALL = -1
 
@@ -210,6 +216,15 @@ def lib():
         if hasattr(L, "rt_trace_stream_color"):
             L.rt_trace_stream_color.argtypes = [vp, C.c_int32, C.POINTER(RayStream), vp, C.c_int32, C.c_int32, C.c_int32, vp]
             L.rt_debug_ray_levels.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int32)]
+        # light sets (builds from before them, loaded for A/B through RTAMD_LIB, lack these)
+        if hasattr(L, "rt_light_set_create"):
+            L.rt_light_set_create.argtypes = [vp, vp, C.c_int32, C.POINTER(vp)]
+            L.rt_light_set_destroy.argtypes = [vp]
+            L.rt_light_set_destroy.restype = None
+            L.rt_light_set_get.argtypes = [vp, C.c_int32, vp, C.POINTER(C.c_int32)]
+            L.rt_render_lit.argtypes = [vp, C.POINTER(Camera), vp, C.POINTER(Frame), vp, C.POINTER(Stats)]
+            L.rt_render_lit_async.argtypes = [vp, C.POINTER(Camera), vp, C.POINTER(Frame)]
+            L.rt_trace_stream_lit.argtypes = [vp, C.c_int32, C.POINTER(RayStream), vp, C.c_int32, C.c_int32, vp]
         _lib = L
     return _lib
 
@@ -544,6 +559,55 @@ class Scene:
         fr = Frame(W, H, mode, shard[0], shard[1], flags, max_depth)
         check(lib().rt_render_async(self.h, C.byref(cam), C.cast(self._keep, C.c_void_p), len(lights), C.byref(fr)))
 
+    # ---- light sets: any number of lights (rt_light_set) ----
+    def light_set(self, lights):
+        """rt_light_set_create: an immutable set of any number of lights ([(pos3, color3) | (vec3, color3, kind)],
+        up to RT_MAX_LIGHT_SET) for render_lit / render_lit_async / trace_stream_lit of this scene."""
+        return LightSet(self, lights)
+
+    def render_lit(self, cam, light_set, W, H, mode=RT_MODE_PRIMARY, shard=(0, 1), flags=0, want_hits=False, max_depth=0):
+        """rt_render_lit: render() with a LightSet in place of the light list."""
+        fr = Frame(W, H, mode, shard[0], shard[1], flags | (RT_FRAME_WRITE_HITS if want_hits else 0), max_depth)
+        rgb = np.zeros((H, W, 3), np.float32)
+        st = Stats()
+        check(lib().rt_render_lit(self.h, C.byref(cam), light_set.h, C.byref(fr), _p(rgb), C.byref(st)))
+        if want_hits:
+            face = np.zeros((H, W), np.int32)
+            t = np.zeros((H, W), np.float32)
+            check(lib().rt_frame_download(self.h, W * H, None, _p(face), _p(t)))
+            return rgb, face, t, st.as_dict()
+        return rgb, st.as_dict()
+
+    def render_lit_async(self, cam, light_set, W, H, mode=RT_MODE_PRIMARY, shard=(0, 1), flags=0, max_depth=0):
+        """rt_render_lit_async: render_async() with a LightSet (kept alive until the next call)."""
+        self._keep = light_set
+        fr = Frame(W, H, mode, shard[0], shard[1], flags, max_depth)
+        check(lib().rt_render_lit_async(self.h, C.byref(cam), light_set.h, C.byref(fr)))
+
+    def trace_stream_lit(self, a, b, light_set, *, mode=RT_MODE_FULL, max_depth=0, reorder=False, wavefront=False,
+                         stats=False, stream=None, out=None):
+        """rt_trace_stream_lit: trace_stream_color() with a LightSet in place of the light list. With stream= the
+        set must stay alive until that stream's work is done."""
+        n = _device_rays(a, "a")
+        if _device_rays(b, "b") != n:
+            raise ValueError("trace_stream_lit: a and b differ in length")
+        given = dict(out or {})
+        res = {}
+        for name, dtype, width, required in self._STREAM_OUTPUTS[RT_RAYS_COLOR]:
+            x = given.pop(name, None)
+            if x is None and (required or out is None):
+                x = _torch_empty(a, (n, 3) if width == 3 else (n,), dtype)
+            if x is not None:
+                _check_device_array(x, dtype, (n, 3) if width == 3 else (n,), name)
+                res[name] = x
+        if given:
+            raise ValueError(f"trace_stream_lit: unknown outputs {sorted(given)}")
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        rs = RayStream(n, a.data_ptr(), b.data_ptr(), ptr("face"), ptr("t"), None, None, None, ptr("rgb"))
+        flags = (RT_RAYS_REORDER if reorder else 0) | (RT_RAYS_STATS if stats else 0) | (RT_RAYS_WAVEFRONT if wavefront else 0)
+        check(lib().rt_trace_stream_lit(self.h, flags, C.byref(rs), light_set.h, mode, max_depth, _stream_ptr(stream)))
+        return res
+
     def synchronize(self):
         st = Stats()
         check(lib().rt_synchronize(self.h, C.byref(st)))
@@ -688,6 +752,37 @@ class Scene:
             self.h = None
 
 
+class LightSet:
+    """rt_light_set: an immutable set of lights of one Scene (Scene.light_set). Keeps its scene alive; destroyed
+    with this object (rt_light_set_destroy waits for the scene's own streams first)."""
+
+    def __init__(self, scene, lights):
+        self.scene = scene
+        self.h = C.c_void_p()
+        arr = Scene._lights(lights)
+        check(lib().rt_light_set_create(scene.h, C.cast(arr, C.c_void_p), len(lights), C.byref(self.h)))
+
+    def __len__(self):
+        n = C.c_int32(0)
+        check(lib().rt_light_set_get(self.h, 0, None, C.byref(n)))
+        return n.value
+
+    def lights(self):
+        """rt_light_set_get: the set's lights in the order calculateColor applies them (points, then directionals)
+        as [(pos3, color3, kind), ...]."""
+        n = len(self)
+        out = (Light * max(n, 1))()
+        m = C.c_int32(0)
+        check(lib().rt_light_set_get(self.h, n, out, C.byref(m)))
+        return [(tuple(out[i].position), tuple(out[i].color), int(out[i].kind)) for i in range(m.value)]
+
+    def __del__(self):
+        # the scene frees the sets it still holds, so a set outliving its scene's handle has nothing left to free
+        if getattr(self, "h", None) and _lib is not None and getattr(self.scene, "h", None):
+            _lib.rt_light_set_destroy(self.h)
+        self.h = None
+
+
 def _dtype_name(x):
     return str(x.dtype).replace("torch.", "")
 
@@ -750,10 +845,12 @@ FRAME_PLAN_FIELDS = ("kernel", "trav", "needs_variants", "grid", "units", "depth
                      "writes_wave_stats", "lpt", "split_ceiling", "rotate_bands", "pipeline_buffers", "full_small_build")
 
 
-def frame_plan(mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_count, variant, record_bytes, has_wide4, alone):
-    """rt_debug_frame_plan: the dispatch plan of such a frame as a dict of ints (no device needed)."""
+def frame_plan(mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_count, variant, record_bytes, has_wide4, alone,
+               mem_lights=None):
+    """rt_debug_frame_plan: the dispatch plan of such a frame as a dict of ints (no device needed). mem_lights: the
+    lights read from a light set in device memory (in[11]; None = the 11-input call)."""
     inp = np.array([mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_count, variant, record_bytes,
-                    int(has_wide4), int(alone)], np.int64)
+                    int(has_wide4), int(alone)] + ([] if mem_lights is None else [int(mem_lights)]), np.int64)
     out = np.zeros(len(FRAME_PLAN_FIELDS), np.int32)
     check(lib().rt_debug_frame_plan(_p(inp), len(inp), _p(out), len(out)))
     return dict(zip(FRAME_PLAN_FIELDS, out.tolist()))

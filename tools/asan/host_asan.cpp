@@ -102,6 +102,47 @@ static void from_arrays() {
   EXPECT(rt_mesh_from_arrays(3, v, nullptr, 1, gneg, good, gm, 0, nullptr, &m) != RT_OK);
 }
 
+// light sets on a host-only scene: create, get and destroy, the invalid arguments, and one set left to the scene
+static void light_sets(rt_scene* s) {
+  std::vector<rt_light> in(7);
+  const int kinds[7] = {1, 0, 1, 0, 0, 1, 0};
+  for (int i = 0; i < 7; i++) {
+    std::memset(&in[i], 0, sizeof in[i]);
+    in[i].position[0] = (float)i;
+    in[i].kind = kinds[i];
+  }
+  rt_light_set* ls = nullptr;
+  EXPECT(rt_light_set_create(s, in.data(), 7, &ls) == RT_OK && ls);
+  std::vector<rt_light> out(7);
+  int32_t n = -1;
+  EXPECT(rt_light_set_get(ls, 7, out.data(), &n) == RT_OK && n == 7);
+  const float want[7] = {1, 3, 4, 6, 0, 2, 5};  // points in array order, then directionals
+  for (int i = 0; i < 7; i++) EXPECT(out[i].position[0] == want[i] && out[i].kind == (i >= 4));
+  EXPECT(rt_light_set_get(ls, 6, out.data(), &n) == RT_ERR_INVALID);
+  EXPECT(rt_light_set_get(ls, 0, nullptr, &n) == RT_OK && n == 7);
+  EXPECT(rt_light_set_get(nullptr, 7, out.data(), &n) == RT_ERR_INVALID);
+  rt_light_set_destroy(ls);
+  rt_light_set_destroy(nullptr);
+  rt_light_set* bad = nullptr;
+  EXPECT(rt_light_set_create(s, in.data(), -1, &bad) == RT_ERR_INVALID && !bad);
+  EXPECT(rt_light_set_create(s, in.data(), RT_MAX_LIGHT_SET + 1, &bad) == RT_ERR_INVALID && !bad);
+  EXPECT(rt_light_set_create(s, nullptr, 3, &bad) == RT_ERR_INVALID && !bad);
+  EXPECT(rt_light_set_create(nullptr, in.data(), 7, &bad) == RT_ERR_INVALID && !bad);
+  EXPECT(rt_light_set_create(s, in.data(), 7, nullptr) == RT_ERR_INVALID);
+  rt_light_set* empty = nullptr;
+  EXPECT(rt_light_set_create(s, nullptr, 0, &empty) == RT_OK && empty);
+  EXPECT(rt_light_set_get(empty, 0, out.data(), &n) == RT_OK && n == 0);
+  rt_light_set_destroy(empty);
+  std::vector<rt_light> big(RT_MAX_LIGHT_SET, in[1]);
+  rt_light_set* full = nullptr;
+  EXPECT(rt_light_set_create(s, big.data(), RT_MAX_LIGHT_SET, &full) == RT_OK && full);
+  rt_camera cam;
+  rt_camera_flycam(64, 48, 0.0f, 0.0f, 0.0f, &cam);
+  const rt_frame fr{64, 48, RT_MODE_FULL, 0, 1, 0, 0};
+  EXPECT(rt_render_lit(s, &cam, full, &fr, nullptr, nullptr) == RT_ERR_NO_DEVICE);
+  // `full` stays alive: rt_scene_destroy frees it
+}
+
 static void scene_roundtrip(const std::string& obj, int box_builder) {
   rt_mesh* m = nullptr;
   if (rt_mesh_load_obj(obj.c_str(), &m) != RT_OK) { std::fprintf(stderr, "skip %s\n", obj.c_str()); return; }
@@ -141,7 +182,8 @@ static void scene_roundtrip(const std::string& obj, int box_builder) {
     l = nullptr;
     if (rt_scene_load(q.c_str(), &o, &l) == RT_OK) rt_scene_destroy(l);
   }
-  rt_scene_destroy(s);
+  light_sets(s);
+  rt_scene_destroy(s);  // frees the set light_sets() left alive
   rt_mesh_destroy(m);
 }
 
