@@ -543,6 +543,71 @@ int rt_render_lit_async(rt_scene* s, const rt_camera* cam, const rt_light_set* l
 int rt_trace_stream_lit(rt_scene* s, int32_t flags, const rt_ray_stream* rays, const rt_light_set* ls,
                         int32_t mode, int32_t max_depth, void* hip_stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * View batches: many cameras of one scene rendered by one launch into device memory, on the caller's stream
+ * (feature test: RT_HAS_VIEW_BATCHES; the API version stays 4). For many small views consumed on the GPU -- a
+ * camera path, multi-view data, one camera per environment -- where a loop of rt_render_async is bound by its
+ * per-frame host cost and rt_frame_download by the trip to host memory.
+ *
+ * rt_render_views(s, views, lights, n_lights, frame, hip_stream)
+ *   Renders views->n_views cameras at frame->width x frame->height with the same lights, mode and max_depth. View
+ *   v, pixel (px, py) -- row 0 = top -- gets exactly the colour, face and t that rt_render writes for
+ *   cameras[v] with RT_FRAME_WRITE_HITS and rt_frame_download returns at (px, py): rgb[((v H + py) W + px) 3 ..],
+ *   face / t[(v H + py) W + px]. Each camera carries its own view matrix, viewport, fovy and aspect ratio.
+ *   cameras is host memory and is read before the call returns; rgb (required), face and t (each optional,
+ *   independent of the other) are device memory of the scene's device. Nothing is written beyond
+ *   n_views * H * W elements.
+ *   frame: mode RT_MODE_PRIMARY or RT_MODE_FULL (RT_MODE_BOX_COLORS: RT_ERR_UNSUPPORTED); max_depth 0 (the
+ *   mode's own) or 1..RT_MAX_TRACE_DEPTH; shard_count 0 or 1 with shard_index 0 (a sharded batch:
+ *   RT_ERR_UNSUPPORTED); flags 0 or RT_FRAME_WRITE_HITS, which is ignored -- the face and t pointers say what is
+ *   written (RT_FRAME_STATS, RT_FRAME_TIMELINE, RT_FRAME_WAVE_STATS: RT_ERR_UNSUPPORTED).
+ *   hip_stream as in rt_trace_stream: non-NULL = everything is enqueued there in order and the call returns
+ *   without waiting for the render; NULL = the scene's own stream, and the call returns after completion.
+ *   Checks, before anything is enqueued: a NULL scene RT_ERR_INVALID; then a host-only scene or no GPU
+ *   RT_ERR_NO_DEVICE; n_views outside 0..RT_MAX_VIEWS, more than RT_MAX_LIGHTS lights, NULL cameras or rgb with
+ *   n_views > 0, an output pointer that is host memory or another device's: RT_ERR_INVALID; a batch of 2^26 or
+ *   more 8x8-pixel blocks (n_views * 4 * ceil(W / 16) * ceil(H / 16); the launch's limit of 2^32 work-items,
+ *   hence also below 2^31 blocks): RT_ERR_INVALID. n_views == 0 returns RT_OK and launches nothing.
+ *   The camera records (the derived camera rt_render computes per frame) are uploaded through pinned memory into
+ *   an array the scene owns, ordered across calls by events: a call may wait on the host for the previous call's
+ *   camera upload, never for a render. The array is reused, so a batch on another stream than the previous
+ *   batch's starts on the device after that batch's kernel: two batches on two streams are both correct but
+ *   run one after the other. Batches on one stream are ordered by the stream. A batch never waits for frames
+ *   of rt_render_async, and they never wait for it.
+ *   A multi-device scene renders the batch on devices[0] alone, as the ray lists.
+ * rt_render_views_lit: the same with a light set (rt_render_lit's result per view). A set of another scene:
+ *   RT_ERR_INVALID. The set must outlive work enqueued on a caller's stream.
+ * Kernels: PRIMARY at depth 1 runs k_views_primary (k_primary_fused's traversal and shading), everything else
+ *   k_views_depth (k_render_depth's level loop; light sets in device memory selected as for frames). Blocks are
+ *   dispatched in plain order: no cost map, no wave split, no timeline -- rt_render keeps those, and stays the
+ *   better call for one large frame.
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_VIEW_BATCHES 1
+#define RT_MAX_VIEWS 65536
+typedef struct rt_view_batch {
+  int32_t n_views;
+  const rt_camera* cameras;  /* host memory [n_views]; may be freed or overwritten as soon as the call returns */
+  float*   rgb;              /* device [n_views][H][W][3], row 0 = top; required when n_views > 0 */
+  int32_t* face;             /* device [n_views][H][W], -1 = miss; optional */
+  float*   t;                /* device [n_views][H][W], +inf = miss; optional, independent of face */
+} rt_view_batch;
+
+int rt_render_views(rt_scene* s, const rt_view_batch* views, const rt_light* lights, int32_t n_lights,
+                    const rt_frame* frame, void* hip_stream);
+int rt_render_views_lit(rt_scene* s, const rt_view_batch* views, const rt_light_set* ls,
+                        const rt_frame* frame, void* hip_stream);
+/* The plan of a batch (host only, no device; csrc/rt_dispatch.h plan_views, which rt_render_views reads for its
+ * kernel and every refusal).
+ * in[0..8] (n_in = 9): mode, max_depth, flags, shard_count, tiles_x, tiles_y (16x16-pixel tiles of one view),
+ * n_views, kernel variant, the number of lights read from a light set in device memory (0 = none).
+ * out[0..6] (n_out = 7): 0 kernel (0 none: an empty or refused batch, 1 k_views_primary, 2 k_views_depth),
+ * 1 recursion limit, 2 units per view (one-wave blocks: 4 tiles_x tiles_y), 3 total blocks, 4 light source
+ * (0 kernel arguments, 1 device memory, 2 device memory with the occluder cache), 5 whether the batch is refused,
+ * 6 the status rt_render_views returns for it (RT_OK when not refused).
+ * Variant bits read: 65536 (k_views_depth also at PRIMARY depth 1), 2097152 (k_views_primary on the binary tree),
+ * 16777216 (no occluder cache); every other bit is ignored. */
+int rt_debug_view_plan(const int64_t in[], int32_t n_in, int64_t out[], int32_t n_out);
+
 /* createDebugRay (flyscene.cpp:129-173) without the GL cylinders: the camera ray through a
  * (float) mouse position and its reflection chain, up to max_depth segments; every segment carries the
  * first ray's traceRay colour; a miss ends the chain with a 10-unit segment. *n_out = segments written. */

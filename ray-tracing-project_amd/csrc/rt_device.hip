@@ -715,6 +715,7 @@ void device_release(rt_scene* s) {
   for (int k = 0; k < s->n_slots; k++)
     if (s->slots[k].stream) (void)hipStreamSynchronize((hipStream_t)s->slots[k].stream);
   ray_stream_release(s);  // the reorder scratch and its event (rt_rays.hip)
+  view_batch_release(s);  // the view batches' camera records and their events (rt_views.hip)
   void* bufs[] = {s->d_nodes, s->d_nodes4, s->d_fshade, s->d_refbox, s->d_mats, s->d_stats,
                   s->d_face_boxcolor, s->asm_buf.d_pack, s->d_pf_check};  // d_tris: inside d_nodes
   for (void* b : bufs)

@@ -1,6 +1,7 @@
 // rt_dispatch.h -- which kernel renders a frame, and in which block order: one pure host function (plan_frame)
 // that rt_device.hip's render_one reads for every such decision, and that rt_debug_frame_plan shows the tests
-// without a device. Host-only: no HIP, no globals, no environment -- a knob that changes the plan is an input.
+// without a device; and the same for a view batch (plan_views, read by rt_views.hip, shown by rt_debug_view_plan).
+// Host-only: no HIP, no globals, no environment -- a knob that changes the plan is an input.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -154,6 +155,65 @@ inline FramePlan plan_frame(const FrameInputs& in) {
     p.split_ceiling = std::max(0, std::min(in.split_kp, quarter)) & ~7;
   if (p.kernel == FK_FULL_MEGAKERNEL && p.full_small_build && may_split && !stats && lds)
     p.split_ceiling = std::max(0, std::min(in.split_k, quarter)) & ~7;
+  return p;
+}
+
+// ---- view batches (rt_views.hip rt_render_views; shown to the tests by rt_debug_view_plan) ----
+// One launch of one-wave blocks in plain order: block b renders view b / units_per_view, logical wave
+// b % units_per_view of it (tile * 4 + quarter). The limit on the blocks is the launch's: a grid holds fewer than
+// 2^32 work-items, 64 per block, so 2^26 blocks and more are refused (which keeps the count below 2^31 as well).
+constexpr int64_t kMaxViewBlocks = ((int64_t)1 << 26) - 1;
+
+enum ViewKernel {
+  VK_NONE = 0,  // an empty batch (or a refused one): nothing to launch
+  VK_PRIMARY,   // k_views_primary: PRIMARY at depth 1 with the lights in the kernel arguments
+  VK_DEPTH,     // k_views_depth: every other depth, FULL, lights read from device memory, VB_GENERIC_DEPTH
+};
+
+struct ViewInputs {
+  int mode = RT_MODE_PRIMARY, max_depth = 0, flags = 0, shard_count = 0;  // rt_frame's, as given
+  int tiles_x = 0, tiles_y = 0;                                           // 16x16-pixel tiles of one view
+  int64_t n_views = 0;
+  int variant = 0;
+  int mem_lights = 0;  // lights the batch reads from a light set in device memory (0 = none: kernel arguments)
+};
+
+struct ViewPlan {
+  ViewKernel kernel = VK_NONE;
+  int depth = 1;                 // the recursion limit (max_depth, or the mode's own)
+  int64_t units_per_view = 0;    // one-wave blocks of a view
+  int64_t total_blocks = 0;
+  int light_source = LS_KERNARG; // k_views_depth's LSRC
+  bool primary_binary_tree = false;  // VB_PRIMARY_BINARY_TREE, as for frames
+  int status = RT_OK;            // not RT_OK: the batch is refused with this status, because of `why`
+  const char* why = "";
+};
+
+inline ViewPlan plan_views(const ViewInputs& in) {
+  ViewPlan p;
+  auto refuse = [&](int status, const char* why) {
+    p.kernel = VK_NONE, p.status = status, p.why = why;
+    return p;
+  };
+  const bool full = in.mode == RT_MODE_FULL;
+  p.depth = in.max_depth > 0 ? in.max_depth : (full ? 2 : 1);
+  p.units_per_view = 4 * (int64_t)in.tiles_x * in.tiles_y;
+  p.light_source = in.mem_lights <= 0 ? LS_KERNARG : (in.variant & VB_NO_OCCLUDER_CACHE) ? LS_MEMORY : LS_MEMORY_CACHED;
+  p.primary_binary_tree = (in.variant & VB_PRIMARY_BINARY_TREE) != 0;
+  if (in.mode == RT_MODE_BOX_COLORS) return refuse(RT_ERR_UNSUPPORTED, "box colours need the scene's per-face colour pass, which a batch leaves out");
+  if (in.mode != RT_MODE_PRIMARY && !full) return refuse(RT_ERR_INVALID, "bad mode");
+  if (in.max_depth < 0 || in.max_depth > RT_MAX_TRACE_DEPTH) return refuse(RT_ERR_INVALID, "max_depth outside 0..RT_MAX_TRACE_DEPTH");
+  if (in.shard_count != 0 && in.shard_count != 1) return refuse(RT_ERR_UNSUPPORTED, "a batch renders whole frames (shard_count must be 0 or 1)");
+  if (in.flags & (RT_FRAME_STATS | RT_FRAME_TIMELINE | RT_FRAME_WAVE_STATS)) return refuse(RT_ERR_UNSUPPORTED, "a batch keeps no counters, timeline or per-wave counts");
+  if (in.flags & ~RT_FRAME_WRITE_HITS) return refuse(RT_ERR_INVALID, "bad flags");
+  if (in.tiles_x <= 0 || in.tiles_y <= 0) return refuse(RT_ERR_INVALID, "empty frame");
+  if (in.n_views < 0 || in.n_views > RT_MAX_VIEWS) return refuse(RT_ERR_INVALID, "n_views outside 0..RT_MAX_VIEWS");
+  // (tiles up to 2^27 a side give 2^56 units, times 2^16 views: saturated so the product stays within 64 bits)
+  p.total_blocks = p.units_per_view > ((int64_t)1 << 40) ? INT64_MAX : p.units_per_view * in.n_views;
+  if (p.total_blocks > kMaxViewBlocks) return refuse(RT_ERR_INVALID, "2^26 or more 8x8-pixel blocks in one batch");
+  if (in.n_views == 0) return p;
+  const bool generic = full || p.depth != 1 || in.mem_lights > 0 || (in.variant & VB_GENERIC_DEPTH);
+  p.kernel = generic ? VK_DEPTH : VK_PRIMARY;
   return p;
 }
 

@@ -340,6 +340,25 @@ extern "C" int rt_debug_frame_plan(const int64_t in[], int32_t n_in, int32_t out
   return RT_OK;
 }
 
+extern "C" int rt_debug_view_plan(const int64_t in[], int32_t n_in, int64_t out[], int32_t n_out) {
+  if (!in || !out || n_in != 9 || n_out != 7) { rt::set_error("rt_debug_view_plan: bad argument"); return RT_ERR_INVALID; }
+  for (int k = 0; k < 9; k++)  // every input fits its field (tiles: up to 2^27 a side, a frame of INT32_MAX pixels)
+    if (in[k] < INT32_MIN || in[k] > INT32_MAX || ((k == 4 || k == 5) && in[k] > (1 << 27))) {
+      rt::set_error("rt_debug_view_plan: input %d out of range", k);
+      return RT_ERR_INVALID;
+    }
+  rt::ViewInputs vi;
+  vi.mode = (int)in[0], vi.max_depth = (int)in[1], vi.flags = (int)in[2], vi.shard_count = (int)in[3];
+  vi.tiles_x = (int)in[4], vi.tiles_y = (int)in[5];
+  vi.n_views = in[6];
+  vi.variant = (int)in[7];
+  vi.mem_lights = (int)in[8];
+  const rt::ViewPlan p = rt::plan_views(vi);
+  const int64_t o[7] = {p.kernel, p.depth, p.units_per_view, p.total_blocks, p.light_source, p.status != RT_OK, p.status};
+  memcpy(out, o, sizeof o);
+  return RT_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Ray streams, host side: the coherence keys (rt_raykey.h, the function k_ray_keys runs) and their grid
 // ------------------------------------------------------------------------------------------------

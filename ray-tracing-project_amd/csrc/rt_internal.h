@@ -327,7 +327,25 @@ struct RayParams {
   const uint32_t* perm;
 };
 
-// host helpers of rt_device.hip shared with rt_rays.hip
+// View batches (rt_render_views): the derived camera of one view -- FrameParams' camera fields, as
+// fill_camera_lights computes them -- one 128-B record per view in a device array the scene owns; a block reads
+// its view's record with scalar loads (the view number is wave-uniform)
+struct alignas(16) ViewCam {
+  float vinv[16];
+  float eye[3];
+  float eye_obj[3];
+  float vp[4];
+  float xscale, yscale;
+  float pad[4];
+};
+static_assert(sizeof(ViewCam) == 128, "camera record must be 128 bytes");
+// the batch's part of the kernel arguments (FrameParams carries the scene, lights, frame shape and output bases)
+struct ViewParams {
+  const ViewCam* cams;      // [n_views]
+  uint32_t units_per_view;  // one-wave blocks per view: block b renders view b / units_per_view
+};
+
+// host helpers of rt_device.hip shared with rt_rays.hip and rt_views.hip
 int check_device_scene(rt_scene* s);  // RT_ERR_NO_DEVICE for a host-only scene; makes the scene's device current
 void fill_scene_params(const rt_scene* s, FrameParams& P);  // clears P, then the scene's part of it
 void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights);
@@ -341,5 +359,7 @@ int fill_light_set(FrameParams& P, const rt_light_set* ls, int rep);
 void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights);
 int check_prefetch_word(rt_scene* s);  // RT_CHECK_PREFETCH debug build; RT_OK otherwise
 int kernel_variant();                  // rt_debug_set_variant's current value
+// rt_rays.hip: a pointer the kernels may dereference (device or managed memory of the scene's device; null passes)
+int check_device_pointer(const rt_scene* s, const void* p, const char* who, const char* what);
 
 }  // namespace rt

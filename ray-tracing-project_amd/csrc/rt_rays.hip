@@ -329,7 +329,9 @@ int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipSt
   return RT_OK;
 }
 
-// A pointer the kernels may dereference: device or managed memory of the scene's device
+}  // namespace
+
+// A pointer the kernels may dereference: device or managed memory of the scene's device (shared with rt_views.hip)
 int check_device_pointer(const rt_scene* s, const void* p, const char* who, const char* what) {
   if (!p) return RT_OK;
   hipPointerAttribute_t a{};
@@ -348,6 +350,8 @@ int check_device_pointer(const rt_scene* s, const void* p, const char* who, cons
   }
   return RT_OK;
 }
+
+namespace {
 
 int check_lights(const rt_light* lights, int32_t n_lights) {
   return (n_lights < 0 || n_lights > RT_MAX_LIGHTS || (n_lights && !lights)) ? RT_ERR_INVALID : RT_OK;

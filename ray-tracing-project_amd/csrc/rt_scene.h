@@ -271,6 +271,21 @@ struct rt_scene {
     uint32_t* d_counts = nullptr;
     int32_t last_levels = -1;    // D of the last RT_RAYS_WAVEFRONT call (-1: none yet)
   } rays;
+  // View batches (rt_views.hip): the camera records of the latest rt_render_views call on the device, and the pinned
+  // buffer they are uploaded from. Grown geometrically; a growth retires the old pair (freeing would wait for the
+  // device), and everything is freed with the scene. ev_upload is recorded after each call's copy (the next call's
+  // host writes to h_cams wait for it), ev_use after its kernel on `last_stream` (a call on another stream waits
+  // for it on the device before it overwrites d_cams).
+  struct ViewScratch {
+    rt::ViewCam* d_cams = nullptr;
+    rt::ViewCam* h_cams = nullptr;  // pinned
+    size_t capacity = 0;            // records
+    bool fresh = true;              // the current pair has not been used yet
+    void* ev_upload = nullptr;
+    void* ev_use = nullptr;
+    void* last_stream = nullptr;
+    std::vector<void*> retired_device, retired_host;
+  } views;
   float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
   bool ray_bounds_valid = false;
   bool pending = false;
@@ -288,6 +303,7 @@ int device_replicate(rt_scene* s);
 int current_device();  // -1 without a GPU
 void device_release(rt_scene* s);
 void ray_stream_release(rt_scene* s);  // rt_rays.hip; the scene's device is current
+void view_batch_release(rt_scene* s);  // rt_views.hip; the scene's device is current
 // world bounds of the scene's vertices, computed at first use (rt_host.cpp)
 const float* scene_ray_bounds(rt_scene* s);
 }  // namespace rt

@@ -46,7 +46,9 @@ EXPORTS = [
     "rt_trace_stream_color", "rt_debug_ray_levels",
     "rt_light_set_create", "rt_light_set_destroy", "rt_light_set_get", "rt_render_lit", "rt_render_lit_async",
     "rt_trace_stream_lit",
+    "rt_render_views", "rt_render_views_lit", "rt_debug_view_plan",
 ]
+RT_MAX_VIEWS = 65536
 RT_MAX_LIGHTS = 32
 RT_MAX_LIGHT_SET = 65536
 VARIANT_MEM_LIGHTS = 8388608         # light sets read from device memory at any count (tests, A/B)
@@ -108,6 +110,11 @@ class RandState(C.Structure):
 class RayStream(C.Structure):
     _fields_ = [("n", C.c_int32), ("a3", C.c_void_p), ("b3", C.c_void_p), ("face", C.c_void_p), ("t", C.c_void_p),
                 ("P3", C.c_void_p), ("N3", C.c_void_p), ("blocked", C.c_void_p), ("rgb3", C.c_void_p)]
+
+
+class ViewBatch(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("cameras", C.c_void_p), ("rgb", C.c_void_p), ("face", C.c_void_p),
+                ("t", C.c_void_p)]
 
 
 class Frame(C.Structure):
@@ -225,6 +232,11 @@ def lib():
             L.rt_render_lit.argtypes = [vp, C.POINTER(Camera), vp, C.POINTER(Frame), vp, C.POINTER(Stats)]
             L.rt_render_lit_async.argtypes = [vp, C.POINTER(Camera), vp, C.POINTER(Frame)]
             L.rt_trace_stream_lit.argtypes = [vp, C.c_int32, C.POINTER(RayStream), vp, C.c_int32, C.c_int32, vp]
+        # view batches (builds from before them, loaded for A/B through RTAMD_LIB, lack these)
+        if hasattr(L, "rt_render_views"):
+            L.rt_render_views.argtypes = [vp, C.POINTER(ViewBatch), vp, C.c_int32, C.POINTER(Frame), vp]
+            L.rt_render_views_lit.argtypes = [vp, C.POINTER(ViewBatch), vp, C.POINTER(Frame), vp]
+            L.rt_debug_view_plan.argtypes = [vp, C.c_int32, vp, C.c_int32]
         _lib = L
     return _lib
 
@@ -608,6 +620,44 @@ class Scene:
         check(lib().rt_trace_stream_lit(self.h, flags, C.byref(rs), light_set.h, mode, max_depth, _stream_ptr(stream)))
         return res
 
+    # ---- view batches: many cameras in one launch, into device tensors ----
+    def render_views(self, cams, lights, W, H, *, mode=RT_MODE_PRIMARY, max_depth=0, want_hits=False, stream=None,
+                     out=None):
+        """rt_render_views / rt_render_views_lit: the cameras `cams` (a sequence of Camera) rendered at W x H with
+        the same lights -- a list of light tuples, or a LightSet, which selects the _lit entry point -- in one launch.
+        Returns a dict of device tensors: rgb float32 [n, H, W, 3] and, with want_hits, face int32 [n, H, W] and t
+        float32 [n, H, W]; view v is bit for bit what render(cams[v], ...) returns. out: a dict of preallocated
+        tensors rgb / face / t (rgb is allocated when missing; face and t are written only when given). stream: as
+        trace_stream -- the batch is enqueued there and the call returns at once; None = the scene's own stream,
+        synchronous."""
+        cams = list(cams)
+        n = len(cams)
+        arr = (Camera * max(n, 1))(*cams)
+        given = dict(out or {})
+        res = {}
+        for name, dtype, shape in (("rgb", "float32", (n, H, W, 3)), ("face", "int32", (n, H, W)), ("t", "float32", (n, H, W))):
+            x = given.pop(name, None)
+            if x is None and (name == "rgb" or (out is None and want_hits)):
+                import torch
+                x = torch.empty(shape, dtype=getattr(torch, dtype), device=torch.device("cuda", self.info()["device"]))
+            if x is not None:
+                _check_device_array(x, dtype, shape, name)
+                res[name] = x
+        if given:
+            raise ValueError(f"render_views: unknown outputs {sorted(given)}")
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        vb = ViewBatch(n, C.cast(arr, C.c_void_p), ptr("rgb"), ptr("face"), ptr("t"))
+        fr = Frame(W, H, mode, 0, 1, 0, max_depth)
+        if isinstance(lights, LightSet):
+            self._keep = lights  # alive while the stream's work may read it (until the next call)
+            check(lib().rt_render_views_lit(self.h, C.byref(vb), lights.h, C.byref(fr), _stream_ptr(stream)))
+        else:
+            lights = lights if lights is not None else []
+            L = self._lights(lights)
+            check(lib().rt_render_views(self.h, C.byref(vb), C.cast(L, C.c_void_p), len(lights), C.byref(fr),
+                                        _stream_ptr(stream)))
+        return res
+
     def synchronize(self):
         st = Stats()
         check(lib().rt_synchronize(self.h, C.byref(st)))
@@ -854,6 +904,19 @@ def frame_plan(mode, max_depth, flags, tiles_x, tiles_y, shard_index, shard_coun
     out = np.zeros(len(FRAME_PLAN_FIELDS), np.int32)
     check(lib().rt_debug_frame_plan(_p(inp), len(inp), _p(out), len(out)))
     return dict(zip(FRAME_PLAN_FIELDS, out.tolist()))
+
+
+VIEW_PLAN_FIELDS = ("kernel", "depth", "units_per_view", "total_blocks", "light_source", "refused", "status")
+
+
+def view_plan(mode, max_depth, tiles_x, tiles_y, n_views, variant=0, mem_lights=0, flags=0, shard_count=0):
+    """rt_debug_view_plan: the plan of such a view batch as a dict of ints (no device needed): kernel 0 none / 1
+    k_views_primary / 2 k_views_depth, the recursion limit, units per view, total blocks, light source, and
+    whether rt_render_views refuses the batch, with the status it returns."""
+    inp = np.array([mode, max_depth, flags, shard_count, tiles_x, tiles_y, n_views, variant, mem_lights], np.int64)
+    out = np.zeros(len(VIEW_PLAN_FIELDS), np.int64)
+    check(lib().rt_debug_view_plan(_p(inp), len(inp), _p(out), len(out)))
+    return dict(zip(VIEW_PLAN_FIELDS, out.tolist()))
 
 
 def flycam(W, H, dx=0.0, dy=0.0, dz=0.0):

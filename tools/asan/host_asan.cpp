@@ -1,7 +1,8 @@
 // Host-side AddressSanitizer / UBSan harness (CPU only; tools/asan/run.sh builds it): drives the host
 // entry points of the C ABI -- OBJ ingest (valid and malformed files), host-only scene creation with
 // both box builders' host path, the BVH validator, the binary scene cache (save, load, and every
-// truncation / byte flip of a small file), PPM writers, lights and camera helpers -- so that heap
+// truncation / byte flip of a small file), PPM writers, lights and camera helpers, light sets and the host-only
+// parts of the view batches (their plan hook, both entry points without a device) -- so that heap
 // errors in the host code surface as sanitizer reports instead of later crashes.
 #include <cstdio>
 #include <cstdlib>
@@ -143,6 +144,49 @@ static void light_sets(rt_scene* s) {
   // `full` stays alive: rt_scene_destroy frees it
 }
 
+// view batches, the host-only parts: the plan hook over valid, refused and malformed inputs, and both entry points
+// on a host-only scene and on NULL arguments (nothing may be read or written before the device check)
+static void view_batches(rt_scene* s) {
+  int64_t out[7];
+  const int64_t ok[9] = {RT_MODE_FULL, 0, 0, 0, 3, 2, 4, 0, 0};
+  EXPECT(rt_debug_view_plan(ok, 9, out, 7) == RT_OK && out[0] == 2 && out[2] == 24 && out[3] == 96 && out[5] == 0);
+  const int64_t box[9] = {RT_MODE_BOX_COLORS, 0, 0, 0, 3, 2, 4, 0, 0};
+  EXPECT(rt_debug_view_plan(box, 9, out, 7) == RT_OK && out[0] == 0 && out[5] == 1 && out[6] == RT_ERR_UNSUPPORTED);
+  const int64_t huge[9] = {RT_MODE_PRIMARY, 0, 0, 0, (int64_t)1 << 27, (int64_t)1 << 27, RT_MAX_VIEWS, 0, 0};
+  EXPECT(rt_debug_view_plan(huge, 9, out, 7) == RT_OK && out[5] == 1 && out[6] == RT_ERR_INVALID);
+  const int64_t wild[9] = {INT64_MAX, INT64_MIN, -1, -1, -1, -1, INT64_MAX, -1, INT64_MIN};
+  EXPECT(rt_debug_view_plan(wild, 9, out, 7) == RT_ERR_INVALID);
+  for (int64_t mode = -2; mode < 5; mode++)
+    for (int64_t n : {(int64_t)-1, (int64_t)0, (int64_t)1, (int64_t)RT_MAX_VIEWS, (int64_t)RT_MAX_VIEWS + 1}) {
+      const int64_t in[9] = {mode, 17, 31, 3, 0, 1 << 27, n, -1, RT_MAX_LIGHT_SET};
+      (void)rt_debug_view_plan(in, 9, out, 7);
+    }
+  EXPECT(rt_debug_view_plan(ok, 8, out, 7) == RT_ERR_INVALID && rt_debug_view_plan(ok, 9, out, 6) == RT_ERR_INVALID);
+  EXPECT(rt_debug_view_plan(nullptr, 9, out, 7) == RT_ERR_INVALID && rt_debug_view_plan(ok, 9, nullptr, 7) == RT_ERR_INVALID);
+
+  rt_camera cams[2];
+  rt_camera_flycam(16, 16, 0.0f, 0.0f, 0.0f, &cams[0]);
+  rt_camera_flycam(16, 16, 1.0f, 0.0f, 0.0f, &cams[1]);
+  std::vector<float> rgb(2 * 16 * 16 * 3, 7.0f);
+  const rt_view_batch vb{2, cams, rgb.data(), nullptr, nullptr};
+  const rt_frame fr{16, 16, RT_MODE_PRIMARY, 0, 1, 0, 0};
+  rt_light l;
+  std::memset(&l, 0, sizeof l);
+  rt_light_set* ls = nullptr;
+  EXPECT(rt_light_set_create(s, &l, 1, &ls) == RT_OK && ls);
+  EXPECT(rt_render_views(s, &vb, &l, 1, &fr, nullptr) == RT_ERR_NO_DEVICE);
+  EXPECT(rt_render_views_lit(s, &vb, ls, &fr, nullptr) == RT_ERR_NO_DEVICE);
+  EXPECT(rt_render_views(s, nullptr, nullptr, 99, nullptr, nullptr) == RT_ERR_NO_DEVICE);
+  EXPECT(rt_render_views_lit(s, nullptr, nullptr, nullptr, nullptr) == RT_ERR_NO_DEVICE);
+  EXPECT(rt_render_views(nullptr, &vb, &l, 1, &fr, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_render_views_lit(nullptr, &vb, ls, &fr, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_render_views(nullptr, nullptr, nullptr, 0, nullptr, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_render_views_lit(nullptr, nullptr, nullptr, nullptr, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_last_error()[0] != 0);
+  for (float v : rgb) EXPECT(v == 7.0f);
+  rt_light_set_destroy(ls);
+}
+
 static void scene_roundtrip(const std::string& obj, int box_builder) {
   rt_mesh* m = nullptr;
   if (rt_mesh_load_obj(obj.c_str(), &m) != RT_OK) { std::fprintf(stderr, "skip %s\n", obj.c_str()); return; }
@@ -183,6 +227,7 @@ static void scene_roundtrip(const std::string& obj, int box_builder) {
     if (rt_scene_load(q.c_str(), &o, &l) == RT_OK) rt_scene_destroy(l);
   }
   light_sets(s);
+  view_batches(s);
   rt_scene_destroy(s);  // frees the set light_sets() left alive
   rt_mesh_destroy(m);
 }
