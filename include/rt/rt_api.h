@@ -608,6 +608,61 @@ int rt_render_views_lit(rt_scene* s, const rt_view_batch* views, const rt_light_
  * 16777216 (no occluder cache); every other bit is ignored. */
 int rt_debug_view_plan(const int64_t in[], int32_t n_in, int64_t out[], int32_t n_out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Supersampled views: several rays per pixel, averaged in the launch (feature test: RT_HAS_SUPERSAMPLING; the API
+ * version stays 4). A sample pattern is S offsets (ox_k, oy_k), 1 <= S <= RT_MAX_SAMPLES, each within [-1, 1].
+ *
+ * Sample k of pixel (px, py) of view v is exactly the pixel rt_render writes at (px, py) for cameras[v] with
+ * viewport[0] replaced by viewport[0] - ox_k and viewport[1] by viewport[1] - oy_k, both float subtractions
+ * (everything else of the camera unchanged): for a viewport origin of (0, 0), the reference's screenToWorld at the
+ * float position (px + ox_k, py + oy_k). The pixel's colour is, per channel, ((c_0 + c_1) + ...) + c_{S-1} in that
+ * order as float additions, divided by (float)S (correctly rounded); each c_k is traceRay's clamped colour (the
+ * background on a primary miss). face and t are sample 0's. One sample at offset (0, 0) writes rt_render_views' bits.
+ *
+ * rt_sample_pattern_grid(nx, ny, out): the centres of an nx x ny grid of cells over the pixel, nx * ny <=
+ *   RT_MAX_SAMPLES (else RT_ERR_INVALID), row-major with j outer: ox = (float)((i + 0.5) / nx - 0.5) computed in
+ *   double, oy likewise from j and ny. 1 x 1 is the single offset (0, 0).
+ * rt_sample_pattern_jittered(nx, ny, rng, out): the same cells with the 0.5 replaced by rt_rand(rng) / (RAND_MAX + 1.0),
+ *   drawn for x and then for y, cell by cell in that order; rng NULL = a fresh generator with seed 1.
+ * rt_render_views_ss(s, views, lights, n_lights, frame, pattern, hip_stream) and
+ * rt_render_views_ss_lit(s, views, ls, frame, pattern, hip_stream): rt_render_views / rt_render_views_lit with the
+ *   pattern. Everything documented there holds: outputs, stream semantics, n_views == 0, host-only scenes, the
+ *   order of the checks, devices[0] for a multi-device scene. pattern is host memory, read before the call
+ *   returns; it travels with the camera records (same staging buffer, same copy, same events). Further refusals,
+ *   after the NULL-argument check: a NULL pattern, n_samples outside 1..RT_MAX_SAMPLES, an offset that is not
+ *   finite or lies outside [-1, 1]: RT_ERR_INVALID; a launch of 2^26 or more one-wave blocks: RT_ERR_INVALID.
+ *   Kernels: k_views_ss_loop -- rt_render_views' 8x8-pixel waves, each lane tracing its pixel's S samples in turn
+ *   (any S; the block count is rt_render_views') -- or k_views_ss_packed -- a wave is 64 / S neighbouring pixels times
+ *   S samples (S = 2, 4, 8, 16, 32, 64: pixel blocks of 8x4, 4x4, 4x2, 2x2, 2x1, 1x1; S times the blocks), the
+ *   samples of a pixel summed across lanes in the order above. Both run trace_depth at every mode and depth. Which
+ *   one a power-of-two S takes by default is measured; variant bit 33554432 selects the other. Every
+ *   other S takes the loop.
+ * rt_render_ss(s, cam, lights, n_lights, frame, pattern, out_rgb): one supersampled frame into host memory
+ *   ([H][W][3]); a one-view batch on the scene's stream into a device buffer the scene owns, then the copy.
+ *   Synchronous.
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_SUPERSAMPLING 1
+#define RT_MAX_SAMPLES 64
+typedef struct rt_sample_pattern {
+  int32_t n_samples;
+  float offsets[RT_MAX_SAMPLES][2];  /* (ox, oy) per sample, in pixels */
+} rt_sample_pattern;
+int rt_sample_pattern_grid(int32_t nx, int32_t ny, rt_sample_pattern* out);
+int rt_sample_pattern_jittered(int32_t nx, int32_t ny, rt_rand_state* rng, rt_sample_pattern* out);
+int rt_render_views_ss(rt_scene* s, const rt_view_batch* views, const rt_light* lights, int32_t n_lights,
+                       const rt_frame* frame, const rt_sample_pattern* pattern, void* hip_stream);
+int rt_render_views_ss_lit(rt_scene* s, const rt_view_batch* views, const rt_light_set* ls, const rt_frame* frame,
+                           const rt_sample_pattern* pattern, void* hip_stream);
+int rt_render_ss(rt_scene* s, const rt_camera* cam, const rt_light* lights, int32_t n_lights, const rt_frame* frame,
+                 const rt_sample_pattern* pattern, float* out_rgb);
+/* The plan of a supersampled batch (host only; plan_views with its sample count). in[0..9] (n_in = 10):
+ * rt_debug_view_plan's nine, then n_samples. out[0..9] (n_out = 10): rt_debug_view_plan's seven -- 0 says which of
+ * rt_render_views' kernels the same batch without a pattern would run; the sample kernels run trace_depth under
+ * either -- then 7 the layout (0 loop, 1 packed), 8 pixels per wave, 9 one-wave blocks per 16x16 tile. With
+ * n_samples = 1 the first seven are rt_debug_view_plan's numbers. For a refused plan rt_last_error holds the reason.
+ * Variant bits read: rt_debug_view_plan's, and 33554432 (the non-default layout of a power-of-two sample count). */
+int rt_debug_sample_plan(const int64_t in[], int32_t n_in, int64_t out[], int32_t n_out);
+
 /* createDebugRay (flyscene.cpp:129-173) without the GL cylinders: the camera ray through a
  * (float) mouse position and its reflection chain, up to max_depth segments; every segment carries the
  * first ray's traceRay colour; a miss ends the chain with a 10-unit segment. *n_out = segments written. */
@@ -687,7 +742,8 @@ int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origi
  * (rt_debug_ray_keys follows it), 8388608 light sets read from device memory at any count (by default only sets
  * beyond RT_MAX_LIGHTS are; lets the tests compare the two paths at 0, 1 and 32 lights; a set of 0 lights has no
  * light to read and keeps the default kernels), 16777216 the memory-lights kernels without the wave-level occluder
- * cache of their shadow packets (A/B and tests). Bits of the variants library
+ * cache of their shadow packets (A/B and tests), 33554432 supersampled view batches in the layout that is not the
+ * default at their sample count (power-of-two counts; A/B and tests). Bits of the variants library
  * only (make variants -> librtamd_variants.so; the product library's rt_render returns
  * RT_ERR_UNSUPPORTED for them): 1 VGPR wave stack, 2 4-wide quantised BVH (scenes of the host builders,
  * which also build that tree), 16 FULL as a stage pipeline (whole frames only: a sharded frame returns

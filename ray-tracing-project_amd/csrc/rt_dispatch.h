@@ -176,7 +176,27 @@ struct ViewInputs {
   int64_t n_views = 0;
   int variant = 0;
   int mem_lights = 0;  // lights the batch reads from a light set in device memory (0 = none: kernel arguments)
+  int samples = 1;     // rays per pixel (rt_render_views_ss); 1: rt_render_views' plan, unchanged
 };
+
+// Supersampled batches (rt_render_views_ss): where the S samples of a pixel sit.
+//   SL_LOOP:   a wave is an 8x8-pixel block as in k_views_depth; each lane traces its pixel's S samples one after
+//              the other (any S).
+//   SL_PACKED: a wave is 64 / S neighbouring pixels times S samples, lane = pixel_in_block * S + k (S a power of
+//              two from 2 to 64). The pixel block is block_w x block_h (sample_block below); a 16x16 tile is 4 S waves.
+enum SampleLayout { SL_LOOP = 0, SL_PACKED = 1 };
+// the layout a power-of-two sample count takes by default; VB_SAMPLE_LAYOUT selects the other one. Measured
+// (tools/supersample_ab.py, profiles/ab/supersample_ab.txt; DESIGN.md "Supersampled views"): at every count from 2
+// to 64 the packed waves were faster than the loop beyond the run-to-run spread in every case on both scenes (device
+// time about 1.3x at S = 2 up to about 7x at S = 64), so every count takes them.
+inline SampleLayout default_sample_layout(int /*samples*/) { return SL_PACKED; }
+// the packed layout's pixel block, as base-2 logarithms: S = 2: 8x4, 4: 4x4, 8: 4x2, 16: 2x2, 32: 2x1, 64: 1x1
+inline void sample_block(int samples, int& lg_samples, int& lg_w, int& lg_h) {
+  lg_samples = 0;
+  while ((1 << lg_samples) < samples) lg_samples++;
+  const int lg_pixels = 6 - lg_samples;
+  lg_w = (lg_pixels + 1) / 2, lg_h = lg_pixels / 2;
+}
 
 struct ViewPlan {
   ViewKernel kernel = VK_NONE;
@@ -185,6 +205,10 @@ struct ViewPlan {
   int64_t total_blocks = 0;
   int light_source = LS_KERNARG; // k_views_depth's LSRC
   bool primary_binary_tree = false;  // VB_PRIMARY_BINARY_TREE, as for frames
+  // supersampled batches (samples = 1: the loop's numbers, which are rt_render_views')
+  SampleLayout layout = SL_LOOP;
+  int pixels_per_wave = 64;      // 64 (loop) or 64 / samples (packed)
+  int waves_per_tile = 4;        // one-wave blocks of a 16x16 tile: 4 (loop) or 4 * samples (packed)
   int status = RT_OK;            // not RT_OK: the batch is refused with this status, because of `why`
   const char* why = "";
 };
@@ -197,7 +221,11 @@ inline ViewPlan plan_views(const ViewInputs& in) {
   };
   const bool full = in.mode == RT_MODE_FULL;
   p.depth = in.max_depth > 0 ? in.max_depth : (full ? 2 : 1);
-  p.units_per_view = 4 * (int64_t)in.tiles_x * in.tiles_y;
+  if (in.samples < 1 || in.samples > RT_MAX_SAMPLES) return refuse(RT_ERR_INVALID, "n_samples outside 1..RT_MAX_SAMPLES");
+  const bool pow2 = in.samples >= 2 && (in.samples & (in.samples - 1)) == 0;  // others always take the loop
+  if (pow2) p.layout = (SampleLayout)(default_sample_layout(in.samples) ^ ((in.variant & VB_SAMPLE_LAYOUT) ? 1 : 0));
+  if (p.layout == SL_PACKED) p.pixels_per_wave = 64 / in.samples, p.waves_per_tile = 4 * in.samples;
+  p.units_per_view = (int64_t)p.waves_per_tile * in.tiles_x * in.tiles_y;
   p.light_source = in.mem_lights <= 0 ? LS_KERNARG : (in.variant & VB_NO_OCCLUDER_CACHE) ? LS_MEMORY : LS_MEMORY_CACHED;
   p.primary_binary_tree = (in.variant & VB_PRIMARY_BINARY_TREE) != 0;
   if (in.mode == RT_MODE_BOX_COLORS) return refuse(RT_ERR_UNSUPPORTED, "box colours need the scene's per-face colour pass, which a batch leaves out");
@@ -210,7 +238,8 @@ inline ViewPlan plan_views(const ViewInputs& in) {
   if (in.n_views < 0 || in.n_views > RT_MAX_VIEWS) return refuse(RT_ERR_INVALID, "n_views outside 0..RT_MAX_VIEWS");
   // (tiles up to 2^27 a side give 2^56 units, times 2^16 views: saturated so the product stays within 64 bits)
   p.total_blocks = p.units_per_view > ((int64_t)1 << 40) ? INT64_MAX : p.units_per_view * in.n_views;
-  if (p.total_blocks > kMaxViewBlocks) return refuse(RT_ERR_INVALID, "2^26 or more 8x8-pixel blocks in one batch");
+  if (p.total_blocks > kMaxViewBlocks)
+    return refuse(RT_ERR_INVALID, p.layout == SL_PACKED ? "2^26 or more one-wave blocks in one batch (packed samples)" : "2^26 or more 8x8-pixel blocks in one batch");
   if (in.n_views == 0) return p;
   const bool generic = full || p.depth != 1 || in.mem_lights > 0 || (in.variant & VB_GENERIC_DEPTH);
   p.kernel = generic ? VK_DEPTH : VK_PRIMARY;

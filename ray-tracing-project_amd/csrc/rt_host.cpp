@@ -359,6 +359,60 @@ extern "C" int rt_debug_view_plan(const int64_t in[], int32_t n_in, int64_t out[
   return RT_OK;
 }
 
+extern "C" int rt_debug_sample_plan(const int64_t in[], int32_t n_in, int64_t out[], int32_t n_out) {
+  if (!in || !out || n_in != 10 || n_out != 10) { rt::set_error("rt_debug_sample_plan: bad argument"); return RT_ERR_INVALID; }
+  for (int k = 0; k < 10; k++)  // as rt_debug_view_plan
+    if (in[k] < INT32_MIN || in[k] > INT32_MAX || ((k == 4 || k == 5) && in[k] > (1 << 27))) {
+      rt::set_error("rt_debug_sample_plan: input %d out of range", k);
+      return RT_ERR_INVALID;
+    }
+  rt::ViewInputs vi;
+  vi.mode = (int)in[0], vi.max_depth = (int)in[1], vi.flags = (int)in[2], vi.shard_count = (int)in[3];
+  vi.tiles_x = (int)in[4], vi.tiles_y = (int)in[5];
+  vi.n_views = in[6];
+  vi.variant = (int)in[7];
+  vi.mem_lights = (int)in[8];
+  vi.samples = (int)in[9];
+  const rt::ViewPlan p = rt::plan_views(vi);
+  if (p.status != RT_OK) rt::set_error("rt_debug_sample_plan: %s", p.why);  // the refusal's message, for the tests
+  const int64_t o[10] = {p.kernel, p.depth, p.units_per_view, p.total_blocks, p.light_source, p.status != RT_OK, p.status,
+                         p.layout, p.pixels_per_wave, p.waves_per_tile};
+  memcpy(out, o, sizeof o);
+  return RT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Sample patterns of supersampled view batches (rt_render_views_ss): one offset per cell of an nx x ny grid over the
+// pixel, cells row-major with j outer; the position within the cell is its centre (grid) or drawn from rng (jittered)
+// ------------------------------------------------------------------------------------------------
+static int sample_cells(const char* who, int32_t nx, int32_t ny, rt_rand_state* rng, bool jitter, rt_sample_pattern* out) {
+  if (!out || nx < 1 || ny < 1 || (int64_t)nx * ny > RT_MAX_SAMPLES) {
+    rt::set_error("%s: %d x %d cells (1..%d samples)", who, nx, ny, RT_MAX_SAMPLES);
+    return RT_ERR_INVALID;
+  }
+  rt_rand_state local;
+  if (jitter && !rng) { rt_rand_seed(&local, 1); rng = &local; }
+  memset(out, 0, sizeof *out);
+  out->n_samples = nx * ny;
+  for (int32_t j = 0; j < ny; j++)
+    for (int32_t i = 0; i < nx; i++) {
+      const double ux = jitter ? rt_rand(rng) / (2147483647 + 1.0) : 0.5;  // x first, then y
+      const double uy = jitter ? rt_rand(rng) / (2147483647 + 1.0) : 0.5;
+      float* o = out->offsets[j * nx + i];
+      o[0] = (float)((i + ux) / nx - 0.5);
+      o[1] = (float)((j + uy) / ny - 0.5);
+    }
+  return RT_OK;
+}
+
+extern "C" int rt_sample_pattern_grid(int32_t nx, int32_t ny, rt_sample_pattern* out) {
+  return sample_cells("rt_sample_pattern_grid", nx, ny, nullptr, false, out);
+}
+
+extern "C" int rt_sample_pattern_jittered(int32_t nx, int32_t ny, rt_rand_state* rng, rt_sample_pattern* out) {
+  return sample_cells("rt_sample_pattern_jittered", nx, ny, rng, true, out);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Ray streams, host side: the coherence keys (rt_raykey.h, the function k_ray_keys runs) and their grid
 // ------------------------------------------------------------------------------------------------

@@ -100,6 +100,8 @@ enum VariantBit : int {
   VB_RAYKEY_ORIGIN_MAJOR = 4194304,  // ray streams: the origin-major key layout instead of octant-major (rt_raykey.h)
   VB_MEM_LIGHTS = 8388608,           // light sets: read the lights from device memory at any count (default: > 32)
   VB_NO_OCCLUDER_CACHE = 16777216,   // the memory-lights kernels without the wave-level occluder cache (A/B, tests)
+  VB_SAMPLE_LAYOUT = 33554432,       // supersampled view batches: the layout that is not the default at that sample
+                                     // count (rt_dispatch.h plan_views; power-of-two counts only)
   // PRIMARY variants that leave the fused kernel
   VB_PRIMARY_UNFUSED = VB_SPLIT_PRIMARY | VB_TWO_RAYS_PER_LANE | VB_PERSISTENT,
   // bits under which VB_DUAL_CHAIN is ignored
@@ -343,6 +345,15 @@ static_assert(sizeof(ViewCam) == 128, "camera record must be 128 bytes");
 struct ViewParams {
   const ViewCam* cams;      // [n_views]
   uint32_t units_per_view;  // one-wave blocks per view: block b renders view b / units_per_view
+};
+
+// Supersampled view batches (rt_render_views_ss): the sample kernels' part of the kernel arguments. The offsets live
+// behind the batch's camera records in the scene's device array (uploaded by the same copy); lg_* are the base-2
+// logarithms of the packed layout's pixel block (block_w * block_h * n_samples = 64) and of the sample count.
+struct SampleParams {
+  const float* offsets;  // [n_samples][2]
+  int32_t n_samples;
+  int32_t lg_samples, lg_block_w, lg_block_h;  // packed layout only
 };
 
 // host helpers of rt_device.hip shared with rt_rays.hip and rt_views.hip

@@ -2115,6 +2115,111 @@ void k_views_depth(FrameParams P, ViewParams V) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Supersampled view batches (rt_views.hip rt_render_views_ss): S rays per pixel, averaged in the launch. Sample k of
+// a pixel is the view's camera with viewport[0..1] - offset k (float subtractions), traced by trace_depth exactly as
+// k_views_depth traces the unshifted one; the pixel is ((c_0 + c_1) + ... + c_{S-1}) / (float)S per channel, float
+// additions in that order and one correctly rounded division. face and t are sample 0's. Two layouts (rt_dispatch.h
+// SampleLayout), both bit-equal to S rt_render frames summed in order.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ ViewCam sample_cam(const ViewCam& cam, float ox, float oy) {
+  ViewCam c = cam;
+  c.vp[0] = cam.vp[0] - ox;
+  c.vp[1] = cam.vp[1] - oy;
+  return c;
+}
+
+// Loop layout: k_views_depth's blocks; the sample index is wave-uniform, so the offsets are scalar loads.
+template <bool HITS, int LSRC = LS_KERNARG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEuSmall)))
+void k_views_ss_loop(FrameParams P, ViewParams V, SampleParams SP) {
+  __shared__ WaveLds<TRAV_B2_LDS, false> lds;
+  typedef const __attribute__((address_space(4))) float* CFloat;
+  const ViewCoord c = view_coord(P, V);
+  const ViewCam cam = load_view_cam(V, c.view);
+  const uint64_t ob = (uint64_t)SP.offsets;
+  const CFloat offs = (CFloat)(((uint64_t)uniform((uint32_t)(ob >> 32)) << 32) | (uint32_t)uniform((uint32_t)ob));
+  const int S = (int)uniform((uint32_t)SP.n_samples);
+  f3 acc{0.0f, 0.0f, 0.0f};
+  Hit h0{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
+  uint32_t face0 = 0xFFFFFFFFu;
+#pragma clang loop unroll(disable)
+  for (int k = 0; k < S; k++) {
+    const ViewCam ck = sample_cam(cam, offs[2 * k], offs[2 * k + 1]);
+    const Ray r = primary_ray(P.sc, ck, c.px, c.py);
+    Hit h;
+    uint32_t face;
+    const f3 col = trace_depth<false, LSRC>(P, r, c.active, lds, 0, nullptr, h, face);
+    if (k == 0) {
+      acc = col;
+      h0 = h;
+      face0 = face;
+    } else {
+      acc = f3{acc.x + col.x, acc.y + col.y, acc.z + col.z};
+    }
+  }
+  if (!c.active) return;
+  const float fs = (float)S;
+  const size_t pix = view_pixel(P, c);
+  P.rgb[3 * pix + 0] = acc.x / fs;
+  P.rgb[3 * pix + 1] = acc.y / fs;
+  P.rgb[3 * pix + 2] = acc.z / fs;
+  if (HITS) {
+    if (P.face_out) P.face_out[pix] = face0 != 0xFFFFFFFFu ? (int32_t)face0 : -1;
+    if (P.t_out) P.t_out[pix] = h0.t;
+  }
+}
+
+// Packed layout (S = 2^SP.lg_samples, 2..64): block b of a view is tile b / (4 S), pixel block b % (4 S) of it,
+// row-major over the tile's (16 >> lg_block_w) x (16 >> lg_block_h) blocks of (1 << lg_block_w) x (1 << lg_block_h)
+// pixels; lane = pixel_in_block * S + k, pixels row-major within the block. Every lane traces one sample, with its
+// offset read per lane (a vector load). The S colours of a pixel are then summed by every lane of the pixel's group
+// as the chain c_0 + c_1 + ... + c_{S-1}, each term read from its lane (ds_bpermute) in that order -- never a
+// butterfly -- and lane k = 0 writes. Lanes of pixels outside the frame trace nothing and write nothing, but stay in
+// the wave to the end: the cross-lane reads need every lane executing.
+template <bool HITS, int LSRC = LS_KERNARG>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kFullWavesPerEuSmall)))
+void k_views_ss_packed(FrameParams P, ViewParams V, SampleParams SP) {
+  __shared__ WaveLds<TRAV_B2_LDS, false> lds;
+  const int lane = threadIdx.x & 63;
+  const uint32_t view = uniform(blockIdx.x / V.units_per_view);
+  const uint32_t w = uniform(blockIdx.x - view * V.units_per_view);
+  const int lgS = (int)uniform((uint32_t)SP.lg_samples), lgW = (int)uniform((uint32_t)SP.lg_block_w),
+            lgH = (int)uniform((uint32_t)SP.lg_block_h);
+  const int tile = (int)(w >> (2 + lgS)), sub = (int)(w & ((4u << lgS) - 1u));
+  const int tx = tile % P.tiles_x, ty = tile / P.tiles_x;
+  const int bx = sub & ((16 >> lgW) - 1), by = sub >> (4 - lgW);
+  const int pib = lane >> lgS, k = lane & ((1 << lgS) - 1);
+  ViewCoord c;
+  c.view = view;
+  c.lane = lane;
+  c.px = tx * 16 + (bx << lgW) + (pib & ((1 << lgW) - 1));
+  c.py = ty * 16 + (by << lgH) + (pib >> lgW);
+  c.active = c.px < P.W && c.py < P.H;
+  const ViewCam cam = load_view_cam(V, view);
+  const ViewCam ck = sample_cam(cam, SP.offsets[2 * k], SP.offsets[2 * k + 1]);
+  const Ray r = primary_ray(P.sc, ck, c.px, c.py);
+  Hit h;
+  uint32_t face0;
+  const f3 col = trace_depth<false, LSRC>(P, r, c.active, lds, 0, nullptr, h, face0);
+  const int first = lane - k;  // the pixel's sample 0
+  f3 acc{__shfl(col.x, first), __shfl(col.y, first), __shfl(col.z, first)};
+  const int S = 1 << lgS;
+#pragma clang loop unroll(disable)
+  for (int j = 1; j < S; j++)
+    acc = f3{acc.x + __shfl(col.x, first + j), acc.y + __shfl(col.y, first + j), acc.z + __shfl(col.z, first + j)};
+  if (!c.active || k != 0) return;
+  const float fs = (float)S;
+  const size_t pix = view_pixel(P, c);
+  P.rgb[3 * pix + 0] = acc.x / fs;
+  P.rgb[3 * pix + 1] = acc.y / fs;
+  P.rgb[3 * pix + 2] = acc.z / fs;
+  if (HITS) {
+    if (P.face_out) P.face_out[pix] = face0 != 0xFFFFFFFFu ? (int32_t)face0 : -1;
+    if (P.t_out) P.t_out[pix] = h.t;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // The A/B kernel variants (RT_KERNEL_VARIANT bits, rt_debug_set_variant) live in rt_variants.hip and are
 // linked only into the variants library (`make variants` -> lib/librtamd_variants.so): the product
 // library's weak default of variant_launch() refuses them with RT_ERR_UNSUPPORTED.

@@ -285,6 +285,9 @@ struct rt_scene {
     void* ev_use = nullptr;
     void* last_stream = nullptr;
     std::vector<void*> retired_device, retired_host;
+    // rt_render_ss: the device frame its one-view batch renders into before the copy to the caller
+    float* d_frame = nullptr;
+    size_t frame_capacity = 0;  // floats
   } views;
   float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
   bool ray_bounds_valid = false;

@@ -120,6 +120,20 @@ double Flyscene::raytraceScene(int width, int height) {
   // the PPM's 0..255 (NaN / negative colours), where writePPMImage's own numbers are reproduced from it
   // up to RT_MAX_LIGHTS lights travel with the call; more (a soft light) go through a light set
   int rrc;
+  if (samples > 0) {  // supersampled: the averaged float frame comes back in host memory and is written as it is
+    rt_sample_pattern pattern;
+    rrc = rt_sample_pattern_grid(samples, samples, &pattern);
+    last_image.assign((size_t)width * height * 3, 0.0f);
+    if (rrc == RT_OK) rrc = rt_render_ss(scene_, &cam, ls.data(), (int32_t)ls.size(), &fr, &pattern, last_image.data());
+    if (rrc == RT_OK) rrc = rt_write_ppm(output.c_str(), last_image.data(), width, height);
+    if (rrc != RT_OK) {
+      fprintf(stderr, "%s\n", rt_last_error());
+      return -1.0;
+    }
+    const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    printf(" ray tracing done! \n\nTime it took to render(in seconds): %.6f (%d x %d samples per pixel)\n", wall, samples, samples);
+    return wall * 1e3;
+  }
   if (ls.size() > (size_t)RT_MAX_LIGHTS) {
     rt_light_set* set = nullptr;
     rrc = rt_light_set_create(scene_, ls.data(), (int32_t)ls.size(), &set);

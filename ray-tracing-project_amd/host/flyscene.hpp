@@ -73,6 +73,7 @@ class Flyscene {
                                          // RENDER_BOUNDINGBOX_COLORED_TRIANGLES (flyscene.hpp:166) with the
                                          // boxes' setRandomColor colours of a fresh process
   std::string output = "result.ppm";
+  int samples = 0;                       // N > 0: an N x N grid of rays per pixel, averaged (rt_render_ss); 0: rt_render
   std::vector<float> last_image;         // [H][W][3] float frame (kept only when the 8-bit path was inexact)
   std::string cache_path;                // binary scene cache: loaded if present, written after a build
   // acceleration structures: the library default (rt_scene_opts_default), the configuration every bench number

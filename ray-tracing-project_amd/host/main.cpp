@@ -2,7 +2,9 @@
 // initialize a Flyscene, optionally move the Flycamera, ray trace, write the PPM.
 //   rt_render_cli <scene.obj> [W H] [--primary] [--dz N] [--out result.ppm] [--device D] [--cache file]
 //                 [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...]
-//                 [--spherical-light X Y Z RADIUS N]
+//                 [--spherical-light X Y Z RADIUS N] [--samples N]
+// --samples N: N x N rays per pixel (N from 1 to 8) on a regular grid, averaged (rt_render_ss; PRIMARY or FULL, at
+// most RT_MAX_LIGHTS lights); without it one ray per pixel through rt_render, as before
 // --spherical-light: the default light is replaced by a white spherical light at (X, Y, Z): N point lights jittered
 // within RADIUS plus the centre, as the reference's addLight('s') builds it (flyscene.cpp:212-239)
 // The scene is built as the library's default (rt_scene_opts_default: the SBVH and the reference box partition
@@ -21,7 +23,7 @@
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    fprintf(stderr, "usage: %s scene.obj [W H] [--primary] [--dz N] [--out file.ppm] [--device D] [--cache file] [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...] [--spherical-light X Y Z RADIUS N]\n",
+    fprintf(stderr, "usage: %s scene.obj [W H] [--primary] [--dz N] [--out file.ppm] [--device D] [--cache file] [--host-build] [--lbvh] [--gpu-boxes] [--box-colors] [--devices all|D0,D1,...] [--spherical-light X Y Z RADIUS N] [--samples N]\n",
             argv[0]);
     return 2;
   }
@@ -34,6 +36,7 @@ int main(int argc, char** argv) {
   bool soft = false;
   float soft_pos[3] = {0, 0, 0}, soft_radius = 0.0f;
   int soft_n = 0;
+  int samples = 0;
   for (int i = 2; i < argc; i++) {
     if (!strcmp(argv[i], "--primary")) mode = RT_MODE_PRIMARY;
     else if (!strcmp(argv[i], "--box-colors")) mode = RT_MODE_BOX_COLORS;
@@ -49,6 +52,10 @@ int main(int argc, char** argv) {
       for (int k = 0; k < 3; k++) soft_pos[k] = (float)atof(argv[++i]);
       soft_radius = (float)atof(argv[++i]);
       soft_n = std::max(0, atoi(argv[++i]));
+    }
+    else if (!strcmp(argv[i], "--samples") && i + 1 < argc) {
+      samples = atoi(argv[++i]);
+      if (samples < 1 || samples > 8) { fprintf(stderr, "--samples: N from 1 to 8\n"); return 2; }
     }
     else if (!strcmp(argv[i], "--devices") && i + 1 < argc) {
       const std::string list = argv[++i];
@@ -90,6 +97,7 @@ int main(int argc, char** argv) {
   }
   scene.mode = mode;
   scene.output = out;
+  scene.samples = samples;
   if (dz != 0.0f) scene.getCamera()->translate(0.0f, 0.0f, dz);
   return scene.raytraceScene() < 0 ? 1 : 0;
 }

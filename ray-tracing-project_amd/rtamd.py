@@ -47,8 +47,12 @@ EXPORTS = [
     "rt_light_set_create", "rt_light_set_destroy", "rt_light_set_get", "rt_render_lit", "rt_render_lit_async",
     "rt_trace_stream_lit",
     "rt_render_views", "rt_render_views_lit", "rt_debug_view_plan",
+    "rt_sample_pattern_grid", "rt_sample_pattern_jittered", "rt_render_views_ss", "rt_render_views_ss_lit",
+    "rt_render_ss", "rt_debug_sample_plan",
 ]
 RT_MAX_VIEWS = 65536
+RT_MAX_SAMPLES = 64
+VARIANT_SAMPLE_LAYOUT = 33554432     # supersampled batches in the non-default layout (tests, A/B)
 RT_MAX_LIGHTS = 32
 RT_MAX_LIGHT_SET = 65536
 VARIANT_MEM_LIGHTS = 8388608         # light sets read from device memory at any count (tests, A/B)
@@ -115,6 +119,14 @@ class RayStream(C.Structure):
 class ViewBatch(C.Structure):
     _fields_ = [("n_views", C.c_int32), ("cameras", C.c_void_p), ("rgb", C.c_void_p), ("face", C.c_void_p),
                 ("t", C.c_void_p)]
+
+
+class SamplePattern(C.Structure):
+    _fields_ = [("n_samples", C.c_int32), ("offsets", (C.c_float * 2) * 64)]
+
+    def array(self):
+        """The offsets as float32 [n_samples, 2]."""
+        return np.array([[o[0], o[1]] for o in self.offsets[:self.n_samples]], np.float32).reshape(-1, 2)
 
 
 class Frame(C.Structure):
@@ -237,6 +249,14 @@ def lib():
             L.rt_render_views.argtypes = [vp, C.POINTER(ViewBatch), vp, C.c_int32, C.POINTER(Frame), vp]
             L.rt_render_views_lit.argtypes = [vp, C.POINTER(ViewBatch), vp, C.POINTER(Frame), vp]
             L.rt_debug_view_plan.argtypes = [vp, C.c_int32, vp, C.c_int32]
+        if hasattr(L, "rt_render_views_ss"):
+            SP = C.POINTER(SamplePattern)
+            L.rt_sample_pattern_grid.argtypes = [C.c_int32, C.c_int32, SP]
+            L.rt_sample_pattern_jittered.argtypes = [C.c_int32, C.c_int32, C.POINTER(RandState), SP]
+            L.rt_render_views_ss.argtypes = [vp, C.POINTER(ViewBatch), vp, C.c_int32, C.POINTER(Frame), SP, vp]
+            L.rt_render_views_ss_lit.argtypes = [vp, C.POINTER(ViewBatch), vp, C.POINTER(Frame), SP, vp]
+            L.rt_render_ss.argtypes = [vp, C.POINTER(Camera), vp, C.c_int32, C.POINTER(Frame), SP, vp]
+            L.rt_debug_sample_plan.argtypes = [vp, C.c_int32, vp, C.c_int32]
         _lib = L
     return _lib
 
@@ -622,14 +642,17 @@ class Scene:
 
     # ---- view batches: many cameras in one launch, into device tensors ----
     def render_views(self, cams, lights, W, H, *, mode=RT_MODE_PRIMARY, max_depth=0, want_hits=False, stream=None,
-                     out=None):
+                     out=None, samples=None):
         """rt_render_views / rt_render_views_lit: the cameras `cams` (a sequence of Camera) rendered at W x H with
         the same lights -- a list of light tuples, or a LightSet, which selects the _lit entry point -- in one launch.
         Returns a dict of device tensors: rgb float32 [n, H, W, 3] and, with want_hits, face int32 [n, H, W] and t
         float32 [n, H, W]; view v is bit for bit what render(cams[v], ...) returns. out: a dict of preallocated
         tensors rgb / face / t (rgb is allocated when missing; face and t are written only when given). stream: as
         trace_stream -- the batch is enqueued there and the call returns at once; None = the scene's own stream,
-        synchronous."""
+        synchronous. samples: a SamplePattern, an (nx, ny) grid or an [S, 2] array of offsets selects
+        rt_render_views_ss / _ss_lit -- every pixel the in-order mean of its S samples, face and t sample 0's; None
+        = one ray per pixel, the plain call."""
+        pat = None if samples is None else sample_pattern(samples)
         cams = list(cams)
         n = len(cams)
         arr = (Camera * max(n, 1))(*cams)
@@ -650,13 +673,31 @@ class Scene:
         fr = Frame(W, H, mode, 0, 1, 0, max_depth)
         if isinstance(lights, LightSet):
             self._keep = lights  # alive while the stream's work may read it (until the next call)
-            check(lib().rt_render_views_lit(self.h, C.byref(vb), lights.h, C.byref(fr), _stream_ptr(stream)))
+            if pat is not None:
+                check(lib().rt_render_views_ss_lit(self.h, C.byref(vb), lights.h, C.byref(fr), C.byref(pat), _stream_ptr(stream)))
+            else:
+                check(lib().rt_render_views_lit(self.h, C.byref(vb), lights.h, C.byref(fr), _stream_ptr(stream)))
         else:
             lights = lights if lights is not None else []
             L = self._lights(lights)
-            check(lib().rt_render_views(self.h, C.byref(vb), C.cast(L, C.c_void_p), len(lights), C.byref(fr),
-                                        _stream_ptr(stream)))
+            if pat is not None:
+                check(lib().rt_render_views_ss(self.h, C.byref(vb), C.cast(L, C.c_void_p), len(lights), C.byref(fr),
+                                               C.byref(pat), _stream_ptr(stream)))
+            else:
+                check(lib().rt_render_views(self.h, C.byref(vb), C.cast(L, C.c_void_p), len(lights), C.byref(fr),
+                                            _stream_ptr(stream)))
         return res
+
+    def render_ss(self, cam, lights, W, H, samples, *, mode=RT_MODE_PRIMARY, max_depth=0):
+        """rt_render_ss: one supersampled frame as a host array rgb float32 [H, W, 3] -- the one-view batch
+        render_views(samples=...) runs, copied to host memory. samples as in render_views."""
+        pat = sample_pattern(samples)
+        rgb = np.zeros((H, W, 3), np.float32)
+        fr = Frame(W, H, mode, 0, 1, 0, max_depth)
+        lights = lights if lights is not None else []
+        L = self._lights(lights)
+        check(lib().rt_render_ss(self.h, C.byref(cam), C.cast(L, C.c_void_p), len(lights), C.byref(fr), C.byref(pat), _p(rgb)))
+        return rgb
 
     def synchronize(self):
         st = Stats()
@@ -917,6 +958,52 @@ def view_plan(mode, max_depth, tiles_x, tiles_y, n_views, variant=0, mem_lights=
     out = np.zeros(len(VIEW_PLAN_FIELDS), np.int64)
     check(lib().rt_debug_view_plan(_p(inp), len(inp), _p(out), len(out)))
     return dict(zip(VIEW_PLAN_FIELDS, out.tolist()))
+
+
+SAMPLE_PLAN_FIELDS = VIEW_PLAN_FIELDS + ("layout", "pixels_per_wave", "waves_per_tile")
+
+
+def sample_plan(mode, max_depth, tiles_x, tiles_y, n_views, n_samples, variant=0, mem_lights=0, flags=0, shard_count=0):
+    """rt_debug_sample_plan: view_plan() of a supersampled batch, plus the layout (0 loop, 1 packed), the pixels of
+    a wave and the one-wave blocks of a 16x16 tile. A refused plan carries the reason in "why"."""
+    inp = np.array([mode, max_depth, flags, shard_count, tiles_x, tiles_y, n_views, variant, mem_lights, n_samples], np.int64)
+    out = np.zeros(len(SAMPLE_PLAN_FIELDS), np.int64)
+    check(lib().rt_debug_sample_plan(_p(inp), len(inp), _p(out), len(out)))
+    d = dict(zip(SAMPLE_PLAN_FIELDS, out.tolist()))
+    d["why"] = lib().rt_last_error().decode() if d["refused"] else ""
+    return d
+
+
+def sample_grid(nx, ny):
+    """rt_sample_pattern_grid: the cell centres of an nx x ny grid over the pixel (nx * ny <= 64), j outer."""
+    p = SamplePattern()
+    check(lib().rt_sample_pattern_grid(nx, ny, C.byref(p)))
+    return p
+
+
+def sample_jittered(nx, ny, rng=None):
+    """rt_sample_pattern_jittered: one sample per cell of the grid, placed by rng (a Rand; None = seed 1): x then
+    y, cell by cell."""
+    p = SamplePattern()
+    check(lib().rt_sample_pattern_jittered(nx, ny, C.byref(rng.st) if rng else None, C.byref(p)))
+    return p
+
+
+def sample_pattern(samples):
+    """A SamplePattern from what render_views(samples=...) accepts: a pattern (returned as it is), an (nx, ny)
+    pair of ints (the grid), or an [S, 2] array of offsets (copied as given; the library checks count and range)."""
+    if isinstance(samples, SamplePattern):
+        return samples
+    if isinstance(samples, tuple) and len(samples) == 2 and all(isinstance(x, (int, np.integer)) for x in samples):
+        return sample_grid(int(samples[0]), int(samples[1]))
+    a = np.asarray(samples, np.float32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"samples: shape {a.shape}, expected (nx, ny) or [S, 2]")
+    p = SamplePattern()
+    p.n_samples = len(a)
+    for k in range(min(len(a), RT_MAX_SAMPLES)):
+        p.offsets[k][0], p.offsets[k][1] = float(a[k, 0]), float(a[k, 1])
+    return p
 
 
 def flycam(W, H, dx=0.0, dy=0.0, dz=0.0):
