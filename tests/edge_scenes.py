@@ -265,3 +265,213 @@ def ref_slab_nan(boxes6, M16, o, d):
         lo = (b[None, :, 0:3] - o2[:, None, :]) / d2[:, None, :]
         hi = (b[None, :, 3:6] - o2[:, None, :]) / d2[:, None, :]
     return (np.isnan(lo) | np.isnan(hi)).any(axis=(1, 2))
+
+
+# ---- mesh edges: odd vertex normals and degenerate faces (tests/test_mesh_edges_host.py holds on the oracle that
+# they reach calculateDistance's norm() == 0 rejection; tests/test_gpu_mesh_edges.py holds the kernels to it) ----
+NORMAL_N = 16                          # quads per side of the normal scene's front grid
+NORMAL_CLASSES = "PPNNZZZTTSSXXUUPP"   # class of a front vertex by its column i = id % 17
+NORMAL_PLANE_Z = 0.375                 # world z of the front grid (the back grid at -0.375), as in the tie scene
+
+
+def _class_normals():
+    t, u = np.radians(70.0), np.radians(50.0)
+    return {"P": (0.0, 0.0, 1.0), "N": (0.0, 0.0, -1.0), "Z": (0.0, 0.0, 0.0), "T": (np.sin(t), 0.0, np.cos(t)),
+            "S": (0.0, 0.0, 3.5), "X": (np.nan, 0.0, 1.0), "U": (0.0, np.sin(u), np.cos(u))}
+
+
+def normal_scene():
+    """A 16x16 quad grid (512 half-quad faces, 17x17 vertices) in the plane z = 0 in front of a 2x2 grid at
+    z = -0.75 (normalisation exactly scale 1, translation (0, 0, 0.375)), with explicit vertex normals: the back
+    grid's are (0, 0, 1); a front vertex takes its class from its column (NORMAL_CLASSES): P (0,0,1), N (0,0,-1),
+    Z the zero vector, T a unit vector 70 degrees from +z towards +x, S (0,0,3.5), X (NaN,0,1), U a unit vector
+    50 degrees from +z towards +y. Where a face's interpolated normal is exactly zero (all-Z faces, the P|N faces
+    where the weights cancel, the Z|T faces on edges that only Z vertices weigh in) the reference rejects the hit
+    and the ray goes on to the back grid. Returns the mesh arrays, vn3 [nv,3] and cls [289] (one character per
+    front vertex)."""
+    v0, f0 = _grid(NORMAL_N, 0.0)
+    v1, f1 = _grid(2, -0.75)
+    v = np.concatenate([v0, v1]).astype(F)
+    f = np.concatenate([f0, f1 + len(v0)]).astype(np.uint32)
+    cls = np.array([NORMAL_CLASSES[i % (NORMAL_N + 1)] for i in range(len(v0))])
+    table = _class_normals()
+    vn = np.array([table[c] for c in cls] + [table["P"]] * len(v1), np.float64).astype(F)
+    return (v, f, np.array([MATERIAL], F), [(len(f), 0)]), vn, cls
+
+
+def normal_lattice_rays():
+    """d = (0, 0, -1) from z = 2 at every pair of the 65 coordinates k / 64 - 0.5 (4,225 rays): hit points exactly
+    on the front grid's vertices, edges and cell midlines."""
+    c = (np.arange(65, dtype=F) / F(64) - F(0.5)).astype(F)
+    x, y = np.meshgrid(c, c, indexing="xy")
+    o = np.stack([x.reshape(-1), y.reshape(-1), np.full(x.size, 2.0)], 1).astype(F)
+    d = np.zeros_like(o)
+    d[:, 2] = -1.0
+    return o, d
+
+
+def normal_random_rays(n=4096, seed=5):
+    """Origins uniform in [-0.8, 0.8]^2 x [0.8, 1.5], aimed at uniform points of [-0.49, 0.49]^2 in the front
+    grid's plane."""
+    rng = np.random.default_rng(seed)
+    o = np.stack([rng.uniform(-0.8, 0.8, n), rng.uniform(-0.8, 0.8, n), rng.uniform(0.8, 1.5, n)], 1)
+    tgt = np.stack([rng.uniform(-0.49, 0.49, n), rng.uniform(-0.49, 0.49, n), np.full(n, NORMAL_PLANE_Z)], 1)
+    d = tgt - o
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return o.astype(F), d.astype(F)
+
+
+def normal_shadow_rays(n=2048, seed=5):
+    """shadow(P, L) from just above the back grid straight up through the front grid: P uniform in
+    [-0.45, 0.45]^2 at z = -0.375 + 1e-3, L = (0, 0, 1)."""
+    rng = np.random.default_rng(seed)
+    P = np.stack([rng.uniform(-0.45, 0.45, n), rng.uniform(-0.45, 0.45, n), np.full(n, -NORMAL_PLANE_Z + 1e-3)], 1)
+    L = np.zeros((n, 3))
+    L[:, 2] = 1.0
+    return P.astype(F), L.astype(F)
+
+
+DEGENERATE_PER_KIND = 6
+
+
+def degenerate_faces(v, f, vn3=None, n=NORMAL_N, seed=7):
+    """The mesh (vertices whose first (n+1)^2 rows are a _grid(n, .) lattice, faces, optional vertex normals)
+    with 4 x DEGENERATE_PER_KIND zero-area faces spread through the face list (the other faces keep their
+    relative order): (a, a, b) and (a, a, a) with a repeated index; three collinear lattice vertices of one
+    row; and two coincident vertices, for which a copy of the lattice's first row (with its normals) is appended
+    to the vertices. Every one has the face normal (0, 0, 0), cross products that are exactly zero and a box of no
+    extent in at least one axis. Returns v, f, vn3 (None if not given), added [24] (the new faces' ids) and
+    new_id [len(f)] (where each face of the input went)."""
+    rng = np.random.default_rng(seed)
+    v = np.asarray(v, F)
+    f = np.asarray(f, np.uint32)
+    nv, row = len(v), n + 1
+    dup = nv + np.arange(row)
+    v2 = np.concatenate([v, v[:row]]).astype(F)
+    vn2 = None if vn3 is None else np.concatenate([np.asarray(vn3, F), np.asarray(vn3, F)[:row]]).astype(F)
+    new = []
+    for k in range(DEGENERATE_PER_KIND):
+        a, b = (int(x) for x in rng.choice(row * row, 2, replace=False))
+        new.append((a, a, b) if k % 2 == 0 else (a, b, b))
+        new.append((a, a, a))
+        j, i = int(rng.integers(0, row)), int(rng.integers(0, row - 2))
+        new.append((j * row + i, j * row + i + 1, j * row + i + 2))
+        i = int(rng.integers(0, row - 1))
+        new.append((i, int(dup[i]), row + i + 1) if k % 2 == 0 else (int(dup[i]), i + 1, i))
+    new = np.array(new, np.uint32)
+    total = len(f) + len(new)
+    added = np.sort(rng.permutation(total)[:len(new)])
+    is_new = np.zeros(total, bool)
+    is_new[added] = True
+    f2 = np.empty((total, 3), np.uint32)
+    f2[is_new] = new
+    f2[~is_new] = f
+    return v2, f2, vn2, added.astype(np.int64), np.flatnonzero(~is_new)
+
+
+MICRO_EXPONENTS = tuple(range(8, 45))  # edge lengths 2^-8 .. 2^-44
+MICRO_PLANE_Z = 0.25                   # world z of the fan (object z = 0; the backdrop at object z = -0.5)
+
+
+def micro_fan_scene():
+    """37 triangles around the origin, triangle k in its own sector of the plane z = 0 with edges of about
+    2^-e, e = 8 .. 44 (O, 2^-e u(phi), 2^-e u(phi + 0.12)), in front of one unit-sized triangle at z = -0.5 (the
+    normalisation is scale 1, translation (0, 0, 0.25): x and y are kept exactly, so the small edges survive).
+    Below about 2^-37 the squared cross products underflow: the area A, the sub-areas and Eigen's squaredNorm
+    become denormal and then zero. The vertex normals are the loader's own. Face e - 8 is the triangle of size
+    2^-e; the last face is the backdrop. Returns the mesh arrays."""
+    vs, fs = [(0.0, 0.0, 0.0)], []
+    for k, e in enumerate(MICRO_EXPONENTS):
+        phi = 2 * np.pi * k / len(MICRO_EXPONENTS)
+        s = 2.0 ** -e
+        vs += [(s * np.cos(phi), s * np.sin(phi), 0.0), (s * np.cos(phi + 0.12), s * np.sin(phi + 0.12), 0.0)]
+        fs.append((0, 2 * k + 1, 2 * k + 2))
+    b = len(vs)
+    vs += [(-0.5, -0.5, -0.5), (0.5, -0.5, -0.5), (0.0, 0.5, -0.5)]
+    fs.append((b, b + 1, b + 2))
+    f = np.array(fs, np.uint32)
+    return np.array(vs, np.float64).astype(F), f, np.array([MATERIAL], F), [(len(f), 0)]
+
+
+def micro_fan_rays():
+    """Rays at every fan triangle's centroid and three edge midpoints (float64 means of the float32 world
+    vertices, rounded once): straight down (d = (0, 0, -1)) from distance 1, and along (0.6, 0, -0.8) from 4 edge
+    lengths away. Returns o [296,3], d [296,3] and tri [296] (the fan triangle aimed at)."""
+    v, f, _, _ = micro_fan_scene()
+    w = v.astype(np.float64)
+    w[:, 2] += MICRO_PLANE_Z
+    os_, ds, tri = [], [], []
+    for k, e in enumerate(MICRO_EXPONENTS):
+        p = w[f[k]]
+        tg = [p.mean(0), (p[0] + p[1]) / 2, (p[1] + p[2]) / 2, (p[2] + p[0]) / 2]
+        for dirn, dist in (((0.0, 0.0, -1.0), 1.0), ((0.6, 0.0, -0.8), 4 * 2.0 ** -e)):
+            dirn = np.array(dirn)
+            for t in tg:
+                os_.append(t - dist * dirn)
+                ds.append(dirn)
+                tri.append(k)
+    return np.array(os_).astype(F), np.array(ds).astype(F), np.array(tri, np.int32)
+
+
+def area_f32(w0, w1, w2):
+    """norm(cross(e0, -e2)) / 2 with e0 = w1 - w0, e2 = w0 - w2 in float32, in Eigen's order (cross by
+    components, x0 + (x1 + x2) sums): the A of interpolateNormal, of the kernels and of the safe-normal flag."""
+    w0, w1, w2 = (np.asarray(x, F) for x in (w0, w1, w2))
+    with np.errstate(all="ignore"):
+        return (_norm_f32(_cross_f32(w1 - w0, -(w0 - w2))) / F(2)).astype(F)
+
+
+def _cross_f32(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], -1).astype(F)
+
+
+def _norm_f32(a):
+    return np.sqrt(a[..., 0] * a[..., 0] + (a[..., 1] * a[..., 1] + a[..., 2] * a[..., 2])).astype(F)
+
+
+def blend_normal_f32(w0, w1, w2, n0, n1, n2, P):
+    """interpolateNormal (flyscene.cpp:572-600) in float32 numpy, kernel-independent: the sub-areas of P against
+    the world vertices w0..w2 [n,3], (n0 a1 / A + n1 a2 / A) + n2 a0 / A with the normalised vertex normals, and
+    Eigen's normalized() (unchanged when the squared norm is not > 0). No inside test: for points that passed it."""
+    w0, w1, w2, n0, n1, n2, P = (np.asarray(x, F) for x in (w0, w1, w2, n0, n1, n2, P))
+    with np.errstate(all="ignore"):
+        e0, e1, e2 = w1 - w0, w2 - w1, w0 - w2
+        a0 = _norm_f32(_cross_f32(e0, P - w0)) / F(2)
+        a1 = _norm_f32(_cross_f32(e1, P - w1)) / F(2)
+        a2 = _norm_f32(_cross_f32(e2, P - w2)) / F(2)
+        A = _norm_f32(_cross_f32(e0, -e2)) / F(2)
+        s = ((n0 * a1[:, None] / A[:, None] + n1 * a2[:, None] / A[:, None]) + n2 * a0[:, None] / A[:, None]).astype(F)
+        z = s[:, 0] * s[:, 0] + (s[:, 1] * s[:, 1] + s[:, 2] * s[:, 2])
+        r = np.sqrt(z).astype(F)
+        return np.where((z > 0)[:, None], s / r[:, None], s).astype(F)
+
+
+def normalized_f32(a):
+    """Eigen's normalized() per row in float32: a / sqrt(|a|^2), a itself when |a|^2 is not > 0 (zero, NaN)."""
+    a = np.asarray(a, F)
+    with np.errstate(all="ignore"):
+        z = a[:, 0] * a[:, 0] + (a[:, 1] * a[:, 1] + a[:, 2] * a[:, 2])
+        return np.where((z > 0)[:, None], a / np.sqrt(z).astype(F)[:, None], a).astype(F)
+
+
+def soundness_scene(seed):
+    """A single 16x16 quad grid in the plane z = 0 (nothing behind it) whose vertex normals are random unit vectors
+    at angles uniform in [0, 75] degrees from +z, except a few vertices exactly at the safe-normal flag's boundary
+    n . n_k = 0.5: (sqrt(3)/2, 0, 0.5) rounded to float32 and its two float neighbours in z. Returns the mesh
+    arrays and vn3."""
+    rng = np.random.default_rng(seed)
+    v, f = _grid(NORMAL_N, 0.0)
+    nv = len(v)
+    ang = np.radians(rng.uniform(0.0, 75.0, nv))
+    az = rng.uniform(0.0, 2 * np.pi, nv)
+    vn = np.stack([np.sin(ang) * np.cos(az), np.sin(ang) * np.sin(az), np.cos(ang)], 1).astype(F)
+    edge = np.array([np.sqrt(3.0) / 2, 0.0, 0.5]).astype(F)
+    for k, vid in enumerate(rng.choice(nv, 12, replace=False)):
+        n = edge.copy()
+        if k % 3 == 1:
+            n[2] = np.nextafter(F(0.5), F(1.0))
+        elif k % 3 == 2:
+            n[2] = np.nextafter(F(0.5), F(0.0))
+        vn[vid] = n
+    return (v, f, np.array([MATERIAL], F), [(len(f), 0)]), vn

@@ -2,7 +2,9 @@
 library named by RTAMD_LIB (lib/librtamd_variants.so: the product kernels plus the A/B kernels of
 rt_variants.hip) and renders, for every A/B variant, bunny (PRIMARY + FULL, 1080p) and the 1M soup (FULL
 640x360, PRIMARY 1000x563) and the 64x40 frame of the tie scene (tests/edge_scenes.py: three faces at
-bit-identical t under every pixel; PRIMARY + FULL) with the default kernels and with the variant. Prints one JSON line:
+bit-identical t under every pixel; PRIMARY + FULL) and of the normal scene (explicit vertex normals whose blend
+is the zero vector, NaN or unnormalised: every A/B kernel's own accept path must reject and accept as the default
+kernels do; PRIMARY + FULL) with the default kernels and with the variant. Prints one JSON line:
 {variant name: [differing cases]}. Not a test module (no test_ functions); needs a GPU."""
 import json
 import os
@@ -28,7 +30,10 @@ def main():
     soup = rt.Scene(mesh, builder=rt.RT_BUILDER_SBVH)
     (v, f, m, g), _ = edge_scenes.tie_scene()
     tie = rt.Scene(rt.Mesh.from_arrays(v, f, m, groups=g), builder=rt.RT_BUILDER_SBVH, min_faces=8)
-    extra = [(tie, 64, 40, rt.RT_MODE_PRIMARY), (tie, 64, 40, rt.RT_MODE_FULL)]
+    (v, f, m, g), vn, _ = edge_scenes.normal_scene()
+    normal = rt.Scene(rt.Mesh.from_arrays(v, f, m, vn3=vn, groups=g), builder=rt.RT_BUILDER_SBVH, min_faces=8)
+    extra = [(tie, 64, 40, rt.RT_MODE_PRIMARY), (tie, 64, 40, rt.RT_MODE_FULL),
+             (normal, 64, 40, rt.RT_MODE_PRIMARY), (normal, 64, 40, rt.RT_MODE_FULL)]
     out = {}
     for name, bits in sorted(VARIANTS_LIB.items()):
         out[name] = [list(map(int, c)) for c in variant_frames_identical(rt, (bunny, soup), bits, extra)]
