@@ -1318,8 +1318,10 @@ static int launch_frame(const FramePlan& plan, rt_scene* s, rt_scene::FrameSlot&
       // RT_LDS_PAD (diagnostics): extra dynamic LDS per block, to cap the resident waves per CU in
       // occupancy experiments (160 KiB / (pad + 1 KiB) blocks per CU)
       const unsigned lds_pad = (unsigned)knob_int("RT_LDS_PAD", 0, INT_MIN, INT_MAX);
-      with_bools([&](auto H, auto B) { hipLaunchKernelGGL((k_primary_fused<H.value, B.value>), g, b, lds_pad, st, P); }, hits,
-                 boxcol);
+      // a frame without the 4-wide tree (none built, or VB_PRIMARY_BINARY_TREE) takes the binary-only instantiation
+      with_bools([&](auto H, auto B, auto WD) {
+        hipLaunchKernelGGL((k_primary_fused<H.value, B.value, WD.value>), g, b, lds_pad, st, P);
+      }, hits, boxcol, P.sc.wide_copy_bytes != 0);
       break;
     }
     case FK_PRIMARY_TRACE_SHADE:

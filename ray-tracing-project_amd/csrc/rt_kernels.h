@@ -293,14 +293,21 @@ template <int PRED>
 __device__ __forceinline__ uint64_t fmask(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, PRED); }
 __device__ __forceinline__ bool lane_in(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
-// Rare path of a candidate (uniform triangle): interpolated normal non-zero (calculateDistance's
-// norm()==0 check, flyscene.cpp:467) and the reference box predicate. All loads wave-uniform.
+// LATE (the octant loops of the binary-only fused PRIMARY kernel, whose slot is an SGPR): the shading record's
+// address is formed inside the uncertified-normal branch from an opaque copy of the slot. Left to itself the
+// compiler makes 48 * slot a 64-bit induction variable of every leaf loop -- 8 SALU per leaf and 2 per record on
+// the scalar chain -- for a branch that certified faces never take (SALU per wave 1,998 -> 1,875 on the 1M
+// soup, profiles/ab/leaf_records_ab.txt). Other kernels keep the plain form: applied to every kernel the same
+// edit changed the low bits of one colour in the wavefront counting kernel.
+template <bool LATE = false>
 __device__ __forceinline__ uint64_t accept_candidate(const DevScene& P, const TriRec64& tr, uint32_t slot, f3 e0, f3 e2,
                                                     f3 a0, f3 a1, f3 a2, f3 p, const Ray& r, uint64_t cand) {
   if (!(tr.box & kSafeNormalBit)) {  // uniform branch: only faces the host could not certify
     const float area0 = norm(a0) / 2, area1 = norm(a1) / 2, area2 = norm(a2) / 2;
     const float area = norm(cross(e0, neg(e2))) / 2;
-    const float* fs = P.fshade + 12 * (size_t)slot;
+    uint32_t us = slot;
+    if constexpr (LATE) asm volatile("" : "+s"(us));
+    const float* fs = P.fshade + 12 * (size_t)us;
     const f3 n0 = ld3(fs), n1 = ld3(fs + 4), n2 = ld3(fs + 8);
     const f3 nn = blend_normal(n0, n1, n2, area0, area1, area2, area);
     cand &= fmask<kFcmpUNE>(norm(nn), 0.0f);
@@ -342,7 +349,7 @@ __device__ __forceinline__ void occ_push(uint32_t* occ, uint32_t slot) {
 // calculateDistance (flyscene.cpp:444-478) against a wave-uniform triangle record, for the lanes of
 // `act`. CLOSEST: update (t, rank, slot) if 0 <= t < best (rank breaks ties as the reference's order
 // does). ANY: any valid t >= 0 (shadow(), flyscene.cpp:519).
-template <bool ANY, bool STATS = false>
+template <bool ANY, bool STATS = false, bool LATE = false>
 __device__ __forceinline__ void test_tri(const DevScene& P, const TriRec64& tr, uint32_t slot, const Ray& r,
                                          uint64_t act, Hit& h, bool& found, uint32_t* cnt = nullptr,
                                          uint64_t entry = ~0ull, bool desc = false, uint32_t* occ = nullptr) {
@@ -406,7 +413,7 @@ __device__ __forceinline__ void test_tri(const DevScene& P, const TriRec64& tr, 
   cand &= ~ballot(dot(n, a2) < 0);
   if (STATS) cnt[ST_WINS] += cand != 0;
   if (cand == 0) return;
-  const bool acc = lane_in(accept_candidate(P, tr, slot, e0, e2, a0, a1, a2, p, r, cand));
+  const bool acc = lane_in(accept_candidate<LATE>(P, tr, slot, e0, e2, a0, a1, a2, p, r, cand));
   if (STATS) cnt[ST_WACCX] += (ballot(acc) & ~entry) != 0;
   if (ANY) {
     // occluder cache (calc_color, memory-lights kernels only; null everywhere else): the slot at which some
@@ -599,7 +606,8 @@ __device__ __forceinline__ void lds_push(uint32_t* slot, uint32_t v) {
 // by the node's order bit for this octant) is pushed at once; both slab tests give the lane masks; an
 // 8-SALU block picks the next node (near child, the one child needed, or the pop marker) and keeps the
 // push only when both children are needed.
-template <bool ANY, int OCT>
+// LATE: accept_candidate's form for the octant loops of the fused PRIMARY kernel.
+template <bool ANY, int OCT, bool LATE = false>
 __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
                                                    uint32_t* lds_stack, uint32_t node, int sp, uint32_t* occ = nullptr) {
   // lanes still tracing: used by the any-hit triangle tests only (a closest-hit lane without a ray
@@ -696,7 +704,7 @@ __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray&
       }
       for (uint32_t k = 0; k < count; k++) {
         const TriRec64 tr = sload_tri(P.tris, first + k);
-        test_tri<ANY>(P, tr, first + k, r, act, h, found, nullptr, ~0ull, false, occ);
+        test_tri<ANY, false, LATE>(P, tr, first + k, r, act, h, found, nullptr, ~0ull, false, occ);
       }
       if (ANY) {
         active = active & !found;
@@ -713,11 +721,11 @@ __device__ __forceinline__ void traverse_fast_from(const DevScene& P, const Ray&
   if (!ANY && !active) h.t = INFINITY;
 }
 
-template <bool ANY, int OCT>
+template <bool ANY, int OCT, bool LATE = false>
 __device__ __forceinline__ void traverse_fast(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
                                               uint32_t* lds_stack, uint32_t* occ = nullptr) {
   if (P.n_nodes == 0) return;
-  traverse_fast_from<ANY, OCT>(P, r, active, h, found, lds_stack, P.root, 0, occ);
+  traverse_fast_from<ANY, OCT, LATE>(P, r, active, h, found, lds_stack, P.root, 0, occ);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -959,7 +967,8 @@ __device__ __forceinline__ void trace(const DevScene& P, const Ray& r, bool acti
 // octants is walked once per octant present, each walk with that octant's lanes only (ballot masks) and
 // the octant loop's cheaper slab test, instead of one generic walk of the union; a one-octant packet is
 // the loop's single iteration. Each lane is traced by exactly one walk, so results are unchanged.
-template <bool ANY, bool STATS, int TRAV, bool WIDE = false, bool SPLIT = false>
+// LATE: the octant loops' accept_candidate form (the fused PRIMARY kernel).
+template <bool ANY, bool STATS, int TRAV, bool WIDE = false, bool SPLIT = false, bool LATE = false>
 __device__ __forceinline__ void trace_oct(const DevScene& P, const Ray& r, bool active, Hit& h, bool& found,
                                           WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt) {
   if (SPLIT && !STATS && TRAV == TRAV_B2_LDS) {
@@ -1017,14 +1026,14 @@ __device__ __forceinline__ void trace_oct(const DevScene& P, const Ray& r, bool 
       }
       if (!STATS && SL) {
         switch (oct) {
-          case 0: traverse_fast<ANY, 0>(P, r, active, h, found, L.stack[wv]); return;
-          case 1: traverse_fast<ANY, 1>(P, r, active, h, found, L.stack[wv]); return;
-          case 2: traverse_fast<ANY, 2>(P, r, active, h, found, L.stack[wv]); return;
-          case 3: traverse_fast<ANY, 3>(P, r, active, h, found, L.stack[wv]); return;
-          case 4: traverse_fast<ANY, 4>(P, r, active, h, found, L.stack[wv]); return;
-          case 5: traverse_fast<ANY, 5>(P, r, active, h, found, L.stack[wv]); return;
-          case 6: traverse_fast<ANY, 6>(P, r, active, h, found, L.stack[wv]); return;
-          default: traverse_fast<ANY, 7>(P, r, active, h, found, L.stack[wv]); return;
+          case 0: traverse_fast<ANY, 0, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 1: traverse_fast<ANY, 1, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 2: traverse_fast<ANY, 2, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 3: traverse_fast<ANY, 3, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 4: traverse_fast<ANY, 4, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 5: traverse_fast<ANY, 5, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          case 6: traverse_fast<ANY, 6, LATE>(P, r, active, h, found, L.stack[wv]); return;
+          default: traverse_fast<ANY, 7, LATE>(P, r, active, h, found, L.stack[wv]); return;
         }
       }
       switch (oct) {
@@ -1041,11 +1050,11 @@ __device__ __forceinline__ void trace_oct(const DevScene& P, const Ray& r, bool 
   }
   trace<ANY, STATS, TRAV>(P, r, active, h, found, L, wv, cnt);
 }
-template <bool STATS, int TRAV, bool WIDE = false>
+template <bool STATS, int TRAV, bool WIDE = false, bool LATE = false>
 __device__ __forceinline__ void trace_closest_oct(const DevScene& P, const Ray& r, bool active, Hit& h,
                                                   WaveLds<TRAV, STATS>& L, int wv, uint32_t* cnt) {
   bool found = false;
-  trace_oct<false, STATS, TRAV, WIDE, false>(P, r, active, h, found, L, wv, cnt);
+  trace_oct<false, STATS, TRAV, WIDE, false, LATE>(P, r, active, h, found, L, wv, cnt);
 }
 // incoherent FULL-mode packets (the generic loop)
 template <bool ANY, bool STATS, int TRAV>
@@ -1529,10 +1538,14 @@ __global__ __launch_bounds__(256) void k_shade_primary(FrameParams P) {
 // PRIMARY as one kernel (default; variant VB_SPLIT_PRIMARY selects the two-kernel form k_trace_primary +
 // k_shade_primary): the traversal, then the shading of the same lane -- the hit record stays in
 // registers instead of a round trip through HBM, and the traversal state is dead by then, so the
-// shading's registers do not add to the traversal's. Resources of the shipped instantiation
-// k_primary_fused<false, false> (make asm -> build/asm/resource.txt, round 5): 59 VGPR, 78 SGPR, no
-// scratch, 8 waves/SIMD. Measured: C3 +2.7% at 4 frames in flight, bunny +4%.
-template <bool HITS, bool BOXCOL = false>
+// shading's registers do not add to the traversal's. Measured: C3 +2.7% at 4 frames in flight, bunny +4%.
+// WIDE: the instantiation for scenes built with the fp32 4-wide tree (eight traverse_wide_fast copies beside
+// the binary loops); it is the kernel as it was. A frame without a wide tree -- the default scene, or
+// VB_PRIMARY_BINARY_TREE -- runs the binary-only instantiation (launch_frame chooses by the frame's
+// DevScene::wide_copy_bytes), which drops the wide copies and takes accept_candidate's LATE form. Resources
+// (make asm -> build/asm/resource.txt), both 8 waves/SIMD without scratch: binary-only 60 VGPR, 78 SGPR, 26
+// SGPR spill lanes, 51,756 B of code; wide 60 VGPR, 78 SGPR, 20 spill lanes, 93,868 B.
+template <bool HITS, bool BOXCOL = false, bool WIDE = true>
 __global__ __launch_bounds__(64 * kTraceWPB) __attribute__((amdgpu_waves_per_eu(kTraceWavesPerEu)))
 void k_primary_fused(FrameParams P) {
   __shared__ WaveLds<TRAV_B2_LDS, false> lds;
@@ -1544,7 +1557,7 @@ void k_primary_fused(FrameParams P) {
   Ray r = primary_ray(P, c.px, c.py);
   asm("" : "+v"(r.o.x), "+v"(r.o.y), "+v"(r.o.z));
   Hit h{INFINITY, 0xFFFFFFFFu, 0xFFFFFFFFu};
-  trace_closest_oct<false, TRAV_B2_LDS, true>(P.sc, r, c.active, h, lds, c.slot, nullptr);
+  trace_closest_oct<false, TRAV_B2_LDS, WIDE, !WIDE>(P.sc, r, c.active, h, lds, c.slot, nullptr);
   tprim[c.lane] = h.t;  // (INFINITY for a miss or an inactive lane)
   if (c.active) shade_primary_pixel<HITS, BOXCOL>(P, r, (size_t)c.py * P.W + c.px, h.t, h.slot);
   wave_clock_end(P, lds.clk, c.lane, c.qw, c.sub >= 0, tprim);
