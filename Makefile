@@ -57,13 +57,21 @@ $(VARLIB): $(PRODUCT_OBJS) $(OBJ)/rt_variants.o
 
 # A/B builds of the same sources with extra device flags (experiments only):
 #   make ablib TAG=noslp EXTRA="-fno-slp-vectorize"  ->  lib/librtamd_noslp.so  (select with RTAMD_LIB)
-AB_SHARED := $(filter-out $(OBJ)/rt_device.o $(OBJ)/rt_rays.o,$(PRODUCT_OBJS))
-ablib: $(PKG)/csrc/rt_device.hip $(PKG)/csrc/rt_rays.hip $(HDRS) $(AB_SHARED)
-	@mkdir -p $(OBJ) $(PKG)/lib
-	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $< -o $(OBJ)/rt_device_$(TAG).o
-	$(HIPCC) $(HIPFLAGS) $(EXTRA) -Wno-unused-result -c $(PKG)/csrc/rt_rays.hip -o $(OBJ)/rt_rays_$(TAG).o
-	$(HIPCC) $(HIPFLAGS) $(EXTRA) -c $(PKG)/csrc/rt_variants.hip -o $(OBJ)/rt_variants_$(TAG).o
-	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(OBJ)/rt_device_$(TAG).o $(OBJ)/rt_rays_$(TAG).o $(OBJ)/rt_variants_$(TAG).o $(AB_SHARED) -lpthread
+# Every .hip that reaches the kernels of rt_kernels.h -- directly or through a header that includes it -- is rebuilt
+# with $(EXTRA) on every call (rt_variants.hip among them); the other objects are the product's.
+empty :=
+space := $(empty) $(empty)
+KERNEL_HDRS := rt_kernels.h $(notdir $(shell grep -l 'include "rt_kernels.h"' $(PKG)/csrc/*.h))
+AB_NAMES  := $(basename $(notdir $(shell grep -lE 'include "($(subst $(space),|,$(KERNEL_HDRS)))"' $(PKG)/csrc/*.hip)))
+AB_OBJS   := $(AB_NAMES:%=$(OBJ)/%_$(TAG).o)
+AB_SHARED := $(filter-out $(AB_NAMES:%=$(OBJ)/%.o),$(PRODUCT_OBJS))
+$(AB_OBJS): $(OBJ)/%_$(TAG).o: $(PKG)/csrc/%.hip $(HDRS) FORCE
+	@mkdir -p $(OBJ)
+	$(HIPCC) $(HIPFLAGS) $(EXTRA) -Wno-unused-result -c $< -o $@
+ablib: $(AB_OBJS) $(AB_SHARED)
+	@mkdir -p $(PKG)/lib
+	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $(PKG)/lib/librtamd_$(TAG).so $(AB_OBJS) $(AB_SHARED) -lpthread
+FORCE:
 
 # debug build of the same sources with every scalar prefetch offset checked on the device (RT_CHECK_PREFETCH:
 # an out-of-range offset is recorded and fails the next rt_synchronize) -> lib/librtamd_pfcheck.so,
@@ -80,13 +88,13 @@ $(PKG)/lib/rt_render_cli: $(PKG)/host/main.cpp $(PKG)/host/flyscene.cpp $(PKG)/h
 oracle:
 	$(MAKE) -C oracle
 
-asm: $(PKG)/csrc/rt_device.hip $(HDRS)
+asm: $(PKG)/csrc/rt_frame.hip $(HDRS)
 	@mkdir -p $(OBJ)/asm
-	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o $(OBJ)/asm/rt_device.s $<
+	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o $(OBJ)/asm/rt_frame.s $<
 	$(HIPCC) $(HIPFLAGS) --cuda-device-only -c -Rpass-analysis=kernel-resource-usage -o /dev/null $< 2> $(OBJ)/asm/resource.txt || true
 
 clean:
 	rm -rf $(OBJ) $(PKG)/lib
 	$(MAKE) -C oracle clean
 
-.PHONY: ablib all variants oracle cli asm clean pfcheck
+.PHONY: FORCE ablib all variants oracle cli asm clean pfcheck

@@ -1,5 +1,5 @@
 // rt_dispatch.h -- which kernel renders a frame, and in which block order: one pure host function (plan_frame)
-// that rt_device.hip's render_one reads for every such decision, and that rt_debug_frame_plan shows the tests
+// that rt_frame.hip's render_one reads for every such decision, and that rt_debug_frame_plan shows the tests
 // without a device; and the same for a view batch (plan_views, read by rt_views.hip, shown by rt_debug_view_plan).
 // Host-only: no HIP, no globals, no environment -- a knob that changes the plan is an input.
 #pragma once

@@ -274,7 +274,7 @@ extern "C" int rt_scene_set_box_colors(rt_scene* s, const float* colors3) {
   if (colors3) memcpy(c.data(), colors3, c.size() * 4);
   else rt_box_colors_random(nb, nullptr, c.data());
   // frames in flight may still read the per-face table: it is rebuilt at the next box-colour frame,
-  // after the scene's streams have drained (rt_device.hip: ensure_face_boxcolor)
+  // after the scene's streams have drained (rt_frame.hip: ensure_face_boxcolor)
   for (auto& r : s->replicas) {  // every device of a multi-device scene renders with the same colours
     r->box_colors = c;
     r->face_boxcolor_valid = false;

@@ -20,11 +20,6 @@ struct uint2 { unsigned int x, y; };
 
 #include "rt_math.h"
 
-struct rt_scene;
-struct rt_light;
-struct rt_light_set;
-struct rt_camera;
-
 namespace rt {
 
 constexpr uint32_t kLeafBit = 0x80000000u;
@@ -289,7 +284,7 @@ struct FrameParams {
   // chunked-XCD order. cost[logical wave] receives the wave's duration in shader cycles (null = off).
   const uint32_t* order;
   uint32_t* cost;
-  // a moving camera's cost map (whole frames, rt_device.hip render_one): each wave also raises cost_dil over the
+  // a moving camera's cost map (whole frames, rt_frame.hip lpt_begin): each wave also raises cost_dil over the
   // (2 dil_r + 1)^2 waves around it in the frame's wave grid (atomic max), so the next frame's order sees each
   // wave's neighbourhood maximum; null = off
   uint32_t* cost_dil;
@@ -356,21 +351,8 @@ struct SampleParams {
   int32_t lg_samples, lg_block_w, lg_block_h;  // packed layout only
 };
 
-// host helpers of rt_device.hip shared with rt_rays.hip and rt_views.hip
-int check_device_scene(rt_scene* s);  // RT_ERR_NO_DEVICE for a host-only scene; makes the scene's device current
-void fill_scene_params(const rt_scene* s, FrameParams& P);  // clears P, then the scene's part of it
-void fill_lights(FrameParams& P, const rt_light* lights, int32_t n_lights);
 // where the lights of a frame or list come from: kernel arguments, a light set's device array, and there with or
 // without the occluder cache (calc_color's LSRC)
 enum LightSource { LS_KERNARG = 0, LS_MEMORY = 1, LS_MEMORY_CACHED = 2 };
-// a light set on the path the current variant selects: LS_KERNARG copies it into P.lights (at most RT_MAX_LIGHTS),
-// otherwise P.light_set is replica `rep`'s device array; returns the LightSource
-int fill_light_set(FrameParams& P, const rt_light_set* ls, int rep);
-// camera and lights of a frame; P.Minv is set (fill_scene_params)
-void fill_camera_lights(FrameParams& P, const rt_camera* cam, const rt_light* lights, int32_t n_lights);
-int check_prefetch_word(rt_scene* s);  // RT_CHECK_PREFETCH debug build; RT_OK otherwise
-int kernel_variant();                  // rt_debug_set_variant's current value
-// rt_rays.hip: a pointer the kernels may dereference (device or managed memory of the scene's device; null passes)
-int check_device_pointer(const rt_scene* s, const void* p, const char* who, const char* what);
 
 }  // namespace rt

@@ -1,5 +1,5 @@
-// rt_kernels.h -- the gfx950 device code of the MI355X ray-traversal hot path, shared by the product
-// library's kernels (rt_device.hip) and the A/B kernel variants (rt_variants.hip, `make variants`).
+// rt_kernels.h -- the gfx950 device code of the MI355X ray-traversal hot path, shared by the product library's
+// kernels (rt_frame.hip, rt_rays.hip, rt_views.hip) and the A/B kernel variants (rt_variants.hip, `make variants`).
 //
 // Hot path (reference: src/flyscene.cpp:299-614):
 //   one wave = one 8x8 pixel tile, one ray per lane; rays generated in registers (traceRayThread +
@@ -2268,6 +2268,14 @@ template <class F, class... Bools>
 void with_bools(F&& f, bool b, Bools... rest) {
   if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
   else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// A runtime LightSource as a template argument: f(std::integral_constant<int, LS_...>{}), around with_bools or
+// inside it, so one generic lambda picks a kernel's LSRC instantiation too.
+template <class F>
+void with_light_source(int ls, F&& f) {
+  if (ls == LS_MEMORY_CACHED) f(std::integral_constant<int, LS_MEMORY_CACHED>{});
+  else if (ls == LS_MEMORY) f(std::integral_constant<int, LS_MEMORY>{});
+  else f(std::integral_constant<int, LS_KERNARG>{});
 }
 
 }  // namespace rt

@@ -9,8 +9,7 @@
 #include <algorithm>
 #include <vector>
 
-#include "rt_dispatch.h"
-#include "rt_kernels.h"
+#include "rt_device.h"
 #include "rt_raykey.h"
 #include "rt_wavefront.h"
 
@@ -68,7 +67,7 @@ ScratchView scratch_view(const rt_scene::RayScratch& r) {
 // (hipFree / hipMalloc: the one place a stream call may stall).
 int ensure_scratch(rt_scene* s, size_t n, size_t tmp_bytes) {
   rt_scene::RayScratch& r = s->rays;
-  if (!r.ev) HIPCHECK(hipEventCreateWithFlags((hipEvent_t*)&r.ev, hipEventDisableTiming));
+  if (const int rc = ensure_event(r.ev)) return rc;
   if (n > r.capacity || tmp_bytes > r.tmp_bytes) HIPCHECK(hipEventSynchronize((hipEvent_t)r.ev));
   if (n > r.capacity) {
     const size_t cap = std::max<size_t>(std::max(n, 2 * r.capacity), 4096);
@@ -187,12 +186,9 @@ int enqueue_rays_depth(rt_scene* s, int flags, RayParams R, FrameParams& P, hipS
   if (reorder && (rc = begin_reorder(s, R, st))) return rc;
   if (stats && (rc = begin_stats(s, P, st))) return rc;
   const int grid = (R.n + 255) / 256;
-  if (lsrc == LS_MEMORY_CACHED)
-    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value, LS_MEMORY_CACHED>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
-  else if (lsrc == LS_MEMORY)
-    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value, LS_MEMORY>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
-  else
-    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  with_light_source(lsrc, [&](auto LS) {
+    with_bools([&](auto ST) { hipLaunchKernelGGL((k_rays_depth<ST.value, decltype(LS)::value>), dim3(grid), dim3(256), 0, st, P, R); }, stats);
+  });
   HIPCHECK(hipGetLastError());
   if (R.perm) {
     HIPCHECK(hipEventRecord((hipEvent_t)s->rays.ev, st));
@@ -218,7 +214,7 @@ WfState wf_view(void* base, size_t n, int D) {
 // room for the state of n rays at D levels; a growth waits for the previous use (as ensure_scratch)
 int ensure_wavefront(rt_scene* s, size_t n, int D) {
   rt_scene::RayScratch& r = s->rays;
-  if (!r.ev) HIPCHECK(hipEventCreateWithFlags((hipEvent_t*)&r.ev, hipEventDisableTiming));
+  if (const int rc = ensure_event(r.ev)) return rc;
   if (!r.d_counts && hipMalloc((void**)&r.d_counts, (RT_MAX_TRACE_DEPTH + 2) * sizeof(uint32_t)) != hipSuccess) {
     (void)hipGetLastError();
     r.d_counts = nullptr;
@@ -313,12 +309,9 @@ int enqueue_wavefront(rt_scene* s, int flags, RayParams R, FrameParams& P, hipSt
     if ((rc = regroup(in))) return rc;  // the hits, for the shade stage
     W.list = in;
     W.mark = (sorting && !last) ? W.s.key_a : nullptr;  // without a sort the hit list is the next level's list
-    if (lsrc == LS_MEMORY_CACHED)
-      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value, LS_MEMORY_CACHED>), grid, block, 0, st, P, W); }, stats);
-    else if (lsrc == LS_MEMORY)
-      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value, LS_MEMORY>), grid, block, 0, st, P, W); }, stats);
-    else
-      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value>), grid, block, 0, st, P, W); }, stats);
+    with_light_source(lsrc, [&](auto LS) {
+      with_bools([&](auto ST) { hipLaunchKernelGGL((k_wf_shade<ST.value, decltype(LS)::value>), grid, block, 0, st, P, W); }, stats);
+    });
     HIPCHECK(hipGetLastError());
     if (W.mark && (rc = regroup(in))) return rc;
   }

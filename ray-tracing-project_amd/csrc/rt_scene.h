@@ -126,7 +126,7 @@ struct PhaseTimer {
 }  // namespace rt
 
 namespace rt {
-struct EnqueueWorker;  // rt_device.hip: a host thread that queues one replica's share of each frame
+struct EnqueueWorker;  // rt_multi.hip: a host thread that queues one replica's share of each frame
 }
 
 // A light set (rt_api.h): the lights in calculateColor's order (points, then directionals; kinds normalised), on the
@@ -150,7 +150,7 @@ struct rt_scene {
   rt_scene& operator=(const rt_scene&) = delete;
   // Multi-device scenes (rt_scene_opts.n_devices > 1): this scene is device 0's replica; replicas[k - 1]
   // renders on opts.devices[k] with its own copy of the device data (peer copies of this scene's buffers)
-  // and its own frame slots. A frame's tiles are split over the replicas as shards (rt_device.hip
+  // and its own frame slots. A frame's tiles are split over the replicas as shards (rt_multi.hip
   // render_multi); each replica packs its tiles and copies them into pinned host memory for assembly.
   std::vector<std::unique_ptr<rt_scene>> replicas;
   bool is_replica = false;  // a replica of another scene (its box colours are set through that scene only)
@@ -158,11 +158,11 @@ struct rt_scene {
   // replicas are released): each replica's launches of a frame are queued by its own host thread
   std::vector<std::shared_ptr<rt::EnqueueWorker>> workers;
   struct Assembly {
-    void* d_pack = nullptr;  // device: this replica's tiles of the last frame, packed (rt_device.hip)
+    void* d_pack = nullptr;  // device: this replica's tiles of the last frame, packed (rt_download.hip)
     void* h_pack = nullptr;  // pinned host copy of it
     size_t bytes = 0;        // capacity of both
   } asm_buf;
-  // Device-side assembly of a multi-device scene's frame (rt_device.hip assemble_device; this scene = device 0):
+  // Device-side assembly of a multi-device scene's frame (rt_download.hip assemble_device; this scene = device 0):
   // every replica's packed tiles land in d_gather (peer copies over xGMI), one kernel places them into d_frame,
   // and one pinned copy brings the frame to the host
   struct DevAssembly {
@@ -225,7 +225,7 @@ struct rt_scene {
     uint32_t* d_wave_stats = nullptr;  // RT_FRAME_WAVE_STATS records (8 words per logical wave)
     size_t wave_stats_waves = 0;
   };
-  // Longest-first dispatch of lone frames (rt_device.hip render_one): the per-wave costs of a recording frame
+  // Longest-first dispatch of lone frames (rt_frame.hip lpt_begin): the per-wave costs of a recording frame
   // and the order k_order_lpt computed from them, valid for frames with the same key. One map per scene, not
   // per frame slot: only a frame alone on the GPU reads or writes it, and such a frame is queued after every
   // earlier frame (and its sort) has finished, so consecutive lone frames share it whatever slot they take
@@ -292,7 +292,7 @@ struct rt_scene {
   float ray_bounds[6] = {0, 0, 0, 0, 0, 0};  // world bounds of the vertices (lo xyz, hi xyz): the ray keys' grid
   bool ray_bounds_valid = false;
   bool pending = false;
-  std::vector<rt_light_set*> light_sets;  // the scene's live light sets (freed with the scene; rt_device.hip)
+  std::vector<rt_light_set*> light_sets;  // the scene's live light sets (freed with the scene; rt_lights.hip)
 };
 
 namespace rt {
@@ -304,6 +304,7 @@ int resolve_devices(rt_scene_opts& o);
 // data peer-copied from s's (rt_device.hip)
 int device_replicate(rt_scene* s);
 int current_device();  // -1 without a GPU
+int kernel_variant();  // rt_debug_set_variant's current value (rt_frame.hip)
 void device_release(rt_scene* s);
 void ray_stream_release(rt_scene* s);  // rt_rays.hip; the scene's device is current
 void view_batch_release(rt_scene* s);  // rt_views.hip; the scene's device is current

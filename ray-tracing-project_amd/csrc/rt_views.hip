@@ -10,8 +10,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "rt_dispatch.h"
-#include "rt_kernels.h"
+#include "rt_device.h"
 
 namespace rt {
 
@@ -20,25 +19,17 @@ template <bool HITS>
 static void launch_views(const ViewPlan& plan, const FrameParams& P, const ViewParams& V, hipStream_t st) {
   const dim3 grid((unsigned)plan.total_blocks), block(64);
   if (plan.kernel == VK_PRIMARY) hipLaunchKernelGGL((k_views_primary<HITS>), grid, block, 0, st, P, V);
-  else if (plan.light_source == LS_MEMORY_CACHED) hipLaunchKernelGGL((k_views_depth<HITS, LS_MEMORY_CACHED>), grid, block, 0, st, P, V);
-  else if (plan.light_source == LS_MEMORY) hipLaunchKernelGGL((k_views_depth<HITS, LS_MEMORY>), grid, block, 0, st, P, V);
-  else hipLaunchKernelGGL((k_views_depth<HITS, LS_KERNARG>), grid, block, 0, st, P, V);
+  else with_light_source(plan.light_source, [&](auto LS) { hipLaunchKernelGGL((k_views_depth<HITS, LS.value>), grid, block, 0, st, P, V); });
 }
 
 // the sample kernels: <HITS> x the light sources, in the layout the plan chose
 template <bool HITS>
 static void launch_views_ss(const ViewPlan& plan, const FrameParams& P, const ViewParams& V, const SampleParams& SP, hipStream_t st) {
   const dim3 grid((unsigned)plan.total_blocks), block(64);
-  const int ls = plan.light_source;
-  if (plan.layout == SL_PACKED) {
-    if (ls == LS_MEMORY_CACHED) hipLaunchKernelGGL((k_views_ss_packed<HITS, LS_MEMORY_CACHED>), grid, block, 0, st, P, V, SP);
-    else if (ls == LS_MEMORY) hipLaunchKernelGGL((k_views_ss_packed<HITS, LS_MEMORY>), grid, block, 0, st, P, V, SP);
-    else hipLaunchKernelGGL((k_views_ss_packed<HITS, LS_KERNARG>), grid, block, 0, st, P, V, SP);
-  } else {
-    if (ls == LS_MEMORY_CACHED) hipLaunchKernelGGL((k_views_ss_loop<HITS, LS_MEMORY_CACHED>), grid, block, 0, st, P, V, SP);
-    else if (ls == LS_MEMORY) hipLaunchKernelGGL((k_views_ss_loop<HITS, LS_MEMORY>), grid, block, 0, st, P, V, SP);
-    else hipLaunchKernelGGL((k_views_ss_loop<HITS, LS_KERNARG>), grid, block, 0, st, P, V, SP);
-  }
+  with_light_source(plan.light_source, [&](auto LS) {
+    if (plan.layout == SL_PACKED) hipLaunchKernelGGL((k_views_ss_packed<HITS, LS.value>), grid, block, 0, st, P, V, SP);
+    else hipLaunchKernelGGL((k_views_ss_loop<HITS, LS.value>), grid, block, 0, st, P, V, SP);
+  });
 }
 
 void view_batch_release(rt_scene* s) {
@@ -92,8 +83,8 @@ int check_sample_pattern(const char* who, const rt_sample_pattern* pattern) {
 // capacity doubles, so the retired buffers together stay below the live one, and all go with the scene.
 int ensure_view_cams(rt_scene* s, size_t n) {
   rt_scene::ViewScratch& v = s->views;
-  if (!v.ev_upload) HIPCHECK(hipEventCreateWithFlags((hipEvent_t*)&v.ev_upload, hipEventDisableTiming));
-  if (!v.ev_use) HIPCHECK(hipEventCreateWithFlags((hipEvent_t*)&v.ev_use, hipEventDisableTiming));
+  int rc;
+  if ((rc = ensure_event(v.ev_upload)) || (rc = ensure_event(v.ev_use))) return rc;
   if (n <= v.capacity) return RT_OK;
   const size_t cap = std::max<size_t>(std::max(n, 2 * v.capacity), 64);
   void *d = nullptr, *h = nullptr;

@@ -202,6 +202,70 @@ def test_device_side_assembly_matches_one_device(rt, soup, bunny, device_assembl
     assert ref8[0].tobytes() == got8[0].tobytes() and ref8[1] == got8[1]
 
 
+# Small frames where the shard layout has edges (tests/test_multigpu_cpu.py SMALL_SHARD_CASES): replicas without a
+# super-tile (40x24 on 3, 16x16 on 5), partial tiles in x and y, super-tiles that overhang the frame (70x70, 17x129)
+SMALL_FRAMES = [(40, 24, 3), (70, 70, 3), (17, 129, 2), (16, 16, 5)]
+
+
+@pytest.fixture(scope="module")
+def small(rt):
+    """A 300-triangle soup on one device and on {0} x n, and the one-device frames of each shape and mode (rendered
+    once): rgb, face, t, the 8-bit frame and its exactness flag."""
+    mesh, _, _ = rt.soup_mesh(300)
+    sc = {n: rt.Scene(mesh, devices=[0] * n) for n in (2, 3, 5)}
+    sc[1] = rt.Scene(mesh)
+    ref = {}
+    for W, H, _ in SMALL_FRAMES:
+        for mode in ("primary", "full"):
+            ref[W, H, mode] = small_frame(rt, sc[1], W, H, mode)
+            assert (ref[W, H, mode][1] >= 0).any()  # the camera sees the soup
+    return {"scenes": sc, "ref": ref}
+
+
+def small_frame(rt, sc, W, H, mode):
+    m = rt.RT_MODE_FULL if mode == "full" else rt.RT_MODE_PRIMARY
+    rgb, face, t, _ = sc.render(rt.flycam(W, H), rt.DEFAULT_LIGHTS, W, H, mode=m, want_hits=True)
+    rgb8, exact = sc.download_rgb8(W, H)
+    return rgb, face, t, rgb8, exact
+
+
+@pytest.mark.parametrize("assembly", ["host", "device"])
+@pytest.mark.parametrize("mode", ["primary", "full"])
+@pytest.mark.parametrize("WHn", SMALL_FRAMES)
+def test_small_frames_on_replicas_equal_one_device(rt, small, request, WHn, mode, assembly):
+    """rt_render + rt_frame_download and the 8-bit frame with its flag, on {0} x n against one device, byte for byte,
+    assembled on the host and on device 0."""
+    W, H, n = WHn
+    if assembly == "device":
+        request.getfixturevalue("device_assembly")
+    got = small_frame(rt, small["scenes"][n], W, H, mode)
+    for a, b in zip(small["ref"][W, H, mode][:4], got[:4]):
+        assert np.asarray(a).tobytes() == np.asarray(b).tobytes()
+    assert got[4] is small["ref"][W, H, mode][4]
+    assert small["scenes"][n].download(W, H).tobytes() == got[0].tobytes()
+
+
+def test_caller_shard_on_small_multi_device_scene(rt, small):
+    """Shard 1 of 3 of a 70x70 frame on {0, 0}: the replicas render shards 1 and 4 of 6 (one super-tile and none);
+    only that shard's pixels of a prefilled buffer change, to the one-device shard's values."""
+    W, H = 70, 70
+    cam = rt.flycam(W, H)
+    L = rt.Scene._lights(rt.DEFAULT_LIGHTS)
+    fr = rt.Frame(W, H, rt.RT_MODE_PRIMARY, 1, 3, 0, 0)
+    bufs = []
+    for sc in (small["scenes"][1], small["scenes"][2]):
+        out = np.full((H, W, 3), -7.0, np.float32)
+        st = rt.Stats()
+        rt.check(rt.lib().rt_render(sc.h, C.byref(cam), C.cast(L, C.c_void_p), len(rt.DEFAULT_LIGHTS), C.byref(fr),
+                                    out.ctypes.data_as(C.c_void_p), C.byref(st)))
+        bufs.append(out)
+    mask = rt.shard_mask(W, H, 1, 3)
+    assert mask.any() and not mask.all()
+    assert bufs[0].tobytes() == bufs[1].tobytes()
+    assert (bufs[1][~mask] == -7.0).all() and not (bufs[1][mask] == -7.0).any()
+    assert bufs[1][mask].tobytes() == small["ref"][W, H, "primary"][0][mask].tobytes()
+
+
 def test_rgb8_exact_flag_on_nan_colours(rt):
     """The exactness flag survives the assembly: a non-integer specular exponent makes pow() of the reference's
     negative R.E base NaN, which survives its max / clamp and which the 8-bit frame

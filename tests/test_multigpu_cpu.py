@@ -52,6 +52,32 @@ def test_shard_tiles_match_library(rt, WH, n):
     assert list(buf) == [full[0][0], full[0][1], -1, -1]
 
 
+# small frames where the shard layout has edges: (W, H, shards) -> the shards that own no super-tile
+SMALL_SHARD_CASES = {(40, 24, 3): [1, 2],  # one super-tile: everything is shard 0's
+                     (70, 70, 3): [],      # 5x5 tiles, four super-tiles, three of them overhang the frame
+                     (17, 129, 2): [],     # partial tiles in x and y, super-tiles stacked in y
+                     (16, 16, 5): [1, 2, 3, 4]}
+
+
+@pytest.mark.parametrize("WHn", sorted(SMALL_SHARD_CASES))
+def test_small_frame_shards_cover_the_frame_once(rt, WHn):
+    """rt_frame_shard_tiles / rt_frame_shard_bytes on small frames: the shards' tile lists are disjoint and together
+    the frame's tiles, a shard without a super-tile lists nothing, and a slice holds the largest shard's slots
+    (a shard's slots: 4x4 per super-tile it owns, whether or not the tiles lie inside the frame)."""
+    W, H, n = WHn
+    tx, ty = (W + 15) // 16, (H + 15) // 16
+    S = 4  # kShardSuperTile (n > 1)
+    n_super = -(-tx // S) * -(-ty // S)
+    lists = [rt.shard_tiles(W, H, k, n) for k in range(n)]
+    every = [t for tiles in lists for t in tiles]
+    assert len(every) == len(set(every))
+    assert set(every) == {(x, y) for y in range(ty) for x in range(tx)}
+    slots = [-(-(n_super - k) // n) * S * S if n_super > k else 0 for k in range(n)]
+    assert all(len(tiles) <= s for tiles, s in zip(lists, slots))
+    assert rt.shard_bytes(W, H, n) == 768 * max(slots)
+    assert [k for k in range(n) if not lists[k]] == SMALL_SHARD_CASES[WHn]
+
+
 def test_default_frames_are_baseline_configs():
     """N = 1: C3's 1920x1080 frame; N > 1: C4's fixed 3840x2160 frame split over the ranks (strong
     scaling), so every multi-GPU line lands on a BASELINE config."""

@@ -18,9 +18,11 @@ for src in $CSRC/*.cpp; do  # every host source the Makefile links (rt_version.c
   $HIPCC $FLAGS $SAN -fno-gpu-sanitize -c $src -o $OUT/$f.o
   OBJS="$OBJS $OUT/$f.o"
 done
+for src in $CSRC/*.hip; do  # every device source the Makefile links (rt_variants.hip is the A/B library's)
+  f=$(basename $src .hip)
+  [ $f = rt_variants ] && continue
+  OBJS="$OBJS ray-tracing-project_amd/build/$f.o"
+done
 $HIPCC $FLAGS $SAN -fno-gpu-sanitize -c tools/asan/host_asan.cpp -o $OUT/host_asan.o
-$HIPCC $SAN -fno-gpu-sanitize --offload-arch=gfx950 -o $OUT/host_asan $OUT/host_asan.o $OBJS \
-    ray-tracing-project_amd/build/rt_device.o ray-tracing-project_amd/build/rt_rays.o ray-tracing-project_amd/build/rt_views.o \
-    ray-tracing-project_amd/build/rt_build.o \
-    ray-tracing-project_amd/build/rt_boxes.o -lpthread
+$HIPCC $SAN -fno-gpu-sanitize --offload-arch=gfx950 -o $OUT/host_asan $OUT/host_asan.o $OBJS -lpthread
 ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $OUT/host_asan scenes

@@ -1,7 +1,7 @@
 """Register / scratch / occupancy report of the device kernels (compile-only, no GPU).
 
 python tools/kernel_resources.py [-D...] [filter ...]
-Compiles csrc/rt_device.hip for gfx950 with the Makefile's flags plus any -D options, and prints
+Compiles csrc/rt_frame.hip (the frame kernels) for gfx950 with the Makefile's flags plus any -D options, and prints
 VGPRs, SGPRs, private scratch bytes per lane and occupancy of every kernel whose mangled name contains
 one of the filters (default: the render kernels). A scratch size > 0 on a hot kernel is a regression to
 look at before measuring anything (the FULL megakernel's allocation is fragile).
@@ -17,7 +17,7 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=o
 
 
 def report(defines, filters):
-    src = os.path.join(ROOT, "ray-tracing-project_amd", "csrc", "rt_device.hip")
+    src = os.path.join(ROOT, "ray-tracing-project_amd", "csrc", "rt_frame.hip")
     cmd = ["/opt/rocm/bin/hipcc"] + FLAGS + defines + ["--cuda-device-only", "-c",
                                                        "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, src]
     txt = subprocess.run(cmd, capture_output=True, text=True).stderr
