@@ -203,6 +203,57 @@ int rt_scene_load(const char* path, const rt_scene_opts* opts, rt_scene** out);
 int rt_scene_ref_boxes(const rt_scene* s, float* bounds6, int32_t* counts, int32_t* face_order);
 
 /* ---------------------------------------------------------------------------------------------
+ * Moving geometry: a scene's vertices updated in place (additive; RT_API_VERSION stays 4)
+ *
+ * rt_scene_update(s, mesh, stats) replaces the scene's geometry by `mesh`, which must have the scene's
+ * topology: the same n_vertices, n_faces and n_materials, and face_vertex_ids and face_material_ids equal
+ * element for element -- anything else returns RT_ERR_INVALID and leaves the scene exactly as it was. Everything
+ * else is read again: vertices, vertex_normals, face_normals, shape_model_matrix and materials (a caller who
+ * keeps the old model matrix writes it into the description; rt_mesh_from_arrays re-ingests moved vertices).
+ *
+ * Contract: after RT_OK every query -- rt_render*, rt_render_lit*, rt_render_views*, rt_render_ss in every
+ * mode and depth, rt_trace_* and rt_trace_stream* under any flags, rt_scene_ref_boxes, rt_scene_ray_bounds,
+ * rt_debug_ray, rt_debug_scene_flags' per-face flags -- gives, bit for bit, what it gives on a scene that
+ * rt_scene_create makes from `mesh` with this scene's options. The per-face data (world vertices, normals,
+ * plane distances, the reference boxes with their ranks, the flags, the static pad, the certificate range) is
+ * derived again by rt_scene_create's own stages; the traversal tree keeps its topology and leaf order and has
+ * its boxes refit, and since results never depend on the builder (rt_scene_opts.builder: the tree only
+ * culls) any conservative tree gives the same bits. Only speed may differ: rt_debug_tree_cost tells when a
+ * scene is better created anew.
+ *
+ * The call is synchronous: it first waits for the scene's frame-slot streams (as rt_synchronize does; the last
+ * frame stays downloadable), for the latest list call (rt_trace_stream*, any flags) on every caller stream that
+ * carried one, and for the latest view batch (batches on several streams run one after the other); on return the
+ * device data is the new geometry. Light sets, frame slots, streams and scratch stay valid. Box colours stay
+ * unless the number of reference boxes changed (then they are "not set yet" again).
+ *
+ * The tree is refit on the device (devices[0]; replicas receive the changed regions by device copy) unless the
+ * scene is host-only or the new coordinates are not finite and below 1e30 in magnitude; then on the host.
+ * Only the refusals (RT_ERR_INVALID, RT_ERR_UNSUPPORTED) leave the scene as it was. After any other error (a
+ * device allocation or copy that failed) the host half already holds the new geometry and the device data may be
+ * old or half-written: update the scene again, successfully, or destroy it before any further query.
+ * Refused: scenes created with wide_tree = 1 return RT_ERR_UNSUPPORTED in this version (the fp32 4-wide
+ * tree's eight octant copies share the node allocation and are not refit).
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_SCENE_UPDATE 1
+typedef struct rt_update_stats {
+  double prep_ms;           /* host: per-vertex / per-face invariants */
+  double boxes_ms;          /* the reference-box partition (by the scene's box_builder) */
+  double records_ms;        /* host: face records (ranks, boxes, flags), pad, certificate range */
+  double upload_ms;         /* host-to-device copies (and the replicas' copies) */
+  double refit_ms;          /* the refit: device events around the kernels, or the host refit's wall time */
+  double total_ms;          /* the whole call after its waits */
+  int32_t bounds_on_device; /* 1: the tree's boxes were refit on the device, 0: on the host */
+  double sah_cost;          /* rt_debug_tree_cost(k_trav 0.7) out[0] after the update */
+} rt_update_stats;
+int rt_scene_update(rt_scene* s, const rt_mesh_desc* mesh, rt_update_stats* stats /* may be NULL */);
+/* The device-form image of the scene's records: which = 0 the binary nodes (64 B each), 1 the triangle records
+ * in leaf order (64 B), 2 the per-slot shading records (48 B). Downloaded from the device for a device scene;
+ * for a host-only scene built the way the upload builds it. *n_bytes = the image's size; out may be NULL
+ * (size query), else capacity_bytes must hold it. */
+int rt_debug_scene_records(rt_scene* s, int32_t which, int64_t capacity_bytes, void* out, int64_t* n_bytes);
+
+/* ---------------------------------------------------------------------------------------------
  * Camera, lights, frames
  * ------------------------------------------------------------------------------------------- */
 typedef struct rt_camera {

@@ -32,6 +32,31 @@ int regrow(T*& ptr, size_t& capacity, size_t want, size_t bytes, hipStream_t st)
   return RT_OK;
 }
 
+// the reference boxes and the materials in their device form (device_upload, rt_scene_update)
+inline std::vector<float> refbox_image(const HostScene& hs) {
+  std::vector<float> rb(8 * hs.boxes.size());
+  for (size_t b = 0; b < hs.boxes.size(); b++)
+    for (int k = 0; k < 3; k++) { rb[8 * b + k] = hs.boxes[b].low[k]; rb[8 * b + 4 + k] = hs.boxes[b].high[k]; }
+  return rb;
+}
+inline std::vector<DevMat> mats_image(const HostScene& hs) {
+  std::vector<DevMat> dm(hs.mats.size());
+  for (size_t m = 0; m < hs.mats.size(); m++) {
+    DevMat& d = dm[m];
+    memset(&d, 0, sizeof d);
+    for (int k = 0; k < 3; k++) { d.ka[k] = hs.mats[m].ka[k]; d.kd[k] = hs.mats[m].kd[k]; d.ks[k] = hs.mats[m].ks[k]; }
+    d.ns = hs.mats[m].shininess;
+  }
+  return dm;
+}
+// device 0's buffer to a replica's, queued on the replica's stream st (its device is current): over xGMI between
+// GPUs with peer access, a plain device copy when both replicas share a GPU
+inline int replica_copy(void* dst, int dst_dev, const void* src, int src_dev, size_t bytes, hipStream_t st) {
+  if (dst_dev == src_dev) HIPCHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+  else HIPCHECK(hipMemcpyPeerAsync(dst, dst_dev, src, src_dev, bytes, st));
+  return RT_OK;
+}
+
 // ---- rt_frame.hip: one device's frame ----
 void fill_scene_params(const rt_scene* s, FrameParams& P);  // clears P, then the scene's part of it
 // camera and lights of a frame; P.Minv is set (fill_scene_params)

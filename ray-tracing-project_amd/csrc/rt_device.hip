@@ -330,26 +330,10 @@ int device_upload(rt_scene* s) {
     if ((rc = dalloc_copy(&s->d_nodes, nullptr, bytes, tot))) return rc;
     s->nodes_bytes = alloc_bytes(bytes);
     pt.mark("alloc");
-    // the device form of the binary records, filled on the host threads (no value-initialisation pass):
-    // pad0 / pad1 = the children's record offsets (prefetch targets) with the octant order bits in their
-    // low bits, interior children as byte offsets of their records (node_offset)
+    // the device form of the binary records (rt_layout.cpp device_node_image), filled on the host threads (no
+    // value-initialisation pass)
     std::unique_ptr<Node64[]> nodes(new Node64[std::max<size_t>(nn, 1)]);
-    {
-      auto pf = [&](uint32_t c) -> uint32_t {
-        return (uint32_t)(64 * (is_leaf(c) ? nn + leaf_first(c) : (size_t)c));
-      };
-      parallel_for(nn, [&](size_t b, size_t e) {
-        for (size_t i = b; i < e; i++) {
-          Node64 nd = hs.nodes[i];
-          const uint32_t order = nd.pad0;  // octant_order() (rt_layout.cpp), moved into the low offset bits
-          nd.pad0 = pf(nd.child0) | (order & 0x3Fu);
-          nd.pad1 = pf(nd.child1) | ((order >> 6) & 0x3u);
-          if (!is_leaf(nd.child0)) nd.child0 *= 64u;
-          if (!is_leaf(nd.child1)) nd.child1 *= 64u;
-          nodes[i] = nd;
-        }
-      });
-    }
+    device_node_image(hs, nodes.get());
     pt.mark("node_prep");
     if (nn && (rc = h2d(s->d_nodes, nodes.get(), nn * 64))) return rc;
     pt.mark("h2d_nodes");
@@ -387,43 +371,21 @@ int device_upload(rt_scene* s) {
   if ((rc = dalloc_copy(&s->d_nodes4, hs.nodes4.data(), hs.nodes4.size() * sizeof(Node4Q), tot))) return rc;
   s->nodes4_bytes = alloc_bytes(hs.nodes4.size() * sizeof(Node4Q));
   {
-    // per-slot shading record (float4 x 3), in the triangle records' (BVH leaf) order: the unit normals of
-    // the slot's face's three vertices (Mesh normals as interpolateNormal normalises them,
-    // flyscene.cpp:599) and the material id in the first .w. Indexed by slot, not face id, so a hit's two
+    // per-slot shading record (rt_layout.cpp device_fshade_image). Indexed by slot, not face id, so a hit's two
     // gathers (triangle record, shading record) are independent and issue together.
     const size_t nsl = hs.tris.size();
     std::unique_ptr<float[]> fsh(new float[std::max<size_t>(12 * nsl, 4)]);  // >= the 16 B an empty copy moves
     if (nsl == 0) std::fill(fsh.get(), fsh.get() + 4, 0.0f);
-    parallel_for(nsl, [&](size_t b, size_t e) {
-      for (size_t sl = b; sl < e; sl++) {
-        const uint32_t f = hs.tris[sl].face;
-        float* r = fsh.get() + 12 * sl;
-        for (int k = 0; k < 3; k++) {
-          const f3 n = hs.vnn[hs.fidx[3 * f + k]];
-          r[4 * k] = n.x; r[4 * k + 1] = n.y; r[4 * k + 2] = n.z; r[4 * k + 3] = 0.0f;
-        }
-        const int32_t m = hs.fmat[f];
-        memcpy(&r[3], &m, 4);
-      }
-    });
+    device_fshade_image(hs, fsh.get());
     pt.mark("fshade_prep");
     if ((rc = dalloc_copy(&s->d_fshade, fsh.get(), 12 * nsl * 4, tot))) return rc;
     s->fshade_bytes = alloc_bytes(12 * nsl * 4);
     pt.mark("h2d_fshade");
   }
-  std::vector<float> rb(8 * hs.boxes.size());
-  for (size_t b = 0; b < hs.boxes.size(); b++) {
-    for (int k = 0; k < 3; k++) { rb[8 * b + k] = hs.boxes[b].low[k]; rb[8 * b + 4 + k] = hs.boxes[b].high[k]; }
-  }
+  const std::vector<float> rb = refbox_image(hs);
   if ((rc = dalloc_copy(&s->d_refbox, rb.data(), rb.size() * 4, tot))) return rc;
   s->refbox_bytes = alloc_bytes(rb.size() * 4);
-  std::vector<DevMat> dm(hs.mats.size());
-  for (size_t m = 0; m < hs.mats.size(); m++) {
-    DevMat& d = dm[m];
-    memset(&d, 0, sizeof d);
-    for (int k = 0; k < 3; k++) { d.ka[k] = hs.mats[m].ka[k]; d.kd[k] = hs.mats[m].kd[k]; d.ks[k] = hs.mats[m].ks[k]; }
-    d.ns = hs.mats[m].shininess;
-  }
+  const std::vector<DevMat> dm = mats_image(hs);
   if ((rc = dalloc_copy(&s->d_mats, dm.data(), dm.size() * sizeof(DevMat), tot))) return rc;
   s->mats_bytes = alloc_bytes(dm.size() * sizeof(DevMat));
   if ((rc = dalloc_copy(&s->d_stats, nullptr, kStatSlots * sizeof(unsigned long long), tot))) return rc;
@@ -442,6 +404,7 @@ void device_release(rt_scene* s) {
   drain_slots_quiet(s);
   ray_stream_release(s);  // the reorder scratch and its event (rt_rays.hip)
   view_batch_release(s);  // the view batches' camera records and their events (rt_views.hip)
+  refit_release(s);       // what rt_scene_update keeps on the device (rt_refit.hip)
   void* bufs[] = {s->d_nodes, s->d_nodes4, s->d_fshade, s->d_refbox, s->d_mats, s->d_stats,
                   s->d_face_boxcolor, s->asm_buf.d_pack, s->d_pf_check};  // d_tris: inside d_nodes
   for (void* b : bufs)
@@ -532,9 +495,7 @@ static int replicate_one(const rt_scene* src, rt_scene* dst) {
   auto copy = [&](auto** d, const void* sp, size_t bytes) -> int {
     HIPCHECK(hipMalloc((void**)d, bytes));
     tot += (int64_t)bytes;
-    if (dev == src->device) HIPCHECK(hipMemcpyAsync(*d, sp, bytes, hipMemcpyDeviceToDevice, st));
-    else HIPCHECK(hipMemcpyPeerAsync(*d, dev, sp, src->device, bytes, st));
-    return RT_OK;
+    return replica_copy(*d, dev, sp, src->device, bytes, st);
   };
   if ((rc = copy(&dst->d_nodes, src->d_nodes, src->nodes_bytes))) return rc;
   dst->d_tris = reinterpret_cast<TriRec64*>(reinterpret_cast<char*>(dst->d_nodes) +

@@ -68,6 +68,58 @@ extern "C" void rt_scene_opts_default(rt_scene_opts* o) {
 // =====================================================================================================
 // Scene creation (host preparation + device upload)
 // =====================================================================================================
+// hoisted per-vertex / per-face invariants (same expressions as flyscene.cpp:449-450,459,574-577,599), of
+// rt_scene_create and rt_scene_update alike: hs holds the topology (nv, nf, fidx)
+void rt::scene_invariants(rt::HostScene& hs, const rt_mesh_desc* d) {
+  memcpy(hs.M, d->shape_model_matrix, 64);
+  rt::affinv(hs.M, hs.Minv);
+  rt::linear_of(hs.Minv, hs.MS);
+  hs.wv.resize(hs.nv);
+  hs.vnn.resize(hs.nv);
+  hs.ov3.resize(3 * (size_t)hs.nv);
+  rt::parallel_for((size_t)hs.nv, [&](size_t b, size_t e) {
+    for (size_t i = b; i < e; i++) {
+      const float* v = d->vertices + 4 * i;
+      memcpy(&hs.ov3[3 * i], v, 12);
+      hs.wv[i] = rt::affv3(hs.M, f3{v[0] / v[3], v[1] / v[3], v[2] / v[3]});
+      const float* n = d->vertex_normals + 3 * i;
+      hs.vnn[i] = rt::normalized(f3{n[0], n[1], n[2]});
+    }
+  });
+  hs.fnn.resize(hs.nf);
+  hs.fdist.resize(hs.nf);
+  rt::parallel_for((size_t)hs.nf, [&](size_t b, size_t e) {
+    for (size_t f = b; f < e; f++) {
+      const float* n = d->face_normals + 3 * f;
+      hs.fnn[f] = rt::normalized(f3{n[0], n[1], n[2]});
+      hs.fdist[f] = rt::dot(hs.fnn[f], hs.wv[hs.fidx[3 * f]]);
+    }
+  });
+  rt::accept_region(hs);
+}
+
+// The reference-box partition by the scene's box_builder, with the ranks: on device `dev` (-1: none) where asked
+// for and possible, else on the host (a face-less scene, non-finite coordinates). v4: the description's vertices.
+int rt::partition_ref_boxes(rt_scene* s, int dev, const float* v4) {
+  rt::HostScene& hs = s->hs;
+  bool boxes_done = false;
+  s->box_builder_used = RT_BOXES_HOST;
+  if (s->opts.box_builder == RT_BOXES_GPU && dev >= 0 && hs.nf > 0) {  // (a face-less scene: host)
+    bool nonfinite = false;
+    const int rc = rt::gpu_build_ref_boxes(dev, hs, v4, s->opts.min_faces, s->opts.max_boxes, &s->boxes_gpu_ms, &nonfinite);
+    if (rc) return rc;
+    if (!nonfinite) {
+      rt::PhaseTimer pr("boxes-gpu");
+      rt::assign_box_ranks(hs);
+      pr.mark("box_ranks");
+      boxes_done = true;
+      s->box_builder_used = RT_BOXES_GPU;
+    }
+  }
+  if (!boxes_done) rt::build_ref_boxes(hs, v4, s->opts.min_faces, s->opts.max_boxes);
+  return RT_OK;
+}
+
 extern "C" int rt_scene_create(const rt_mesh_desc* d, const rt_scene_opts* opts, rt_scene** out) {
   if (!d || !out) { rt::set_error("rt_scene_create: null argument"); return RT_ERR_INVALID; }
   *out = nullptr;
@@ -116,9 +168,6 @@ extern "C" int rt_scene_create(const rt_mesh_desc* d, const rt_scene_opts* opts,
   rt::HostScene& hs = s->hs;
   hs.nv = d->n_vertices;
   hs.nf = d->n_faces;
-  memcpy(hs.M, d->shape_model_matrix, 64);
-  rt::affinv(hs.M, hs.Minv);
-  rt::linear_of(hs.Minv, hs.MS);
   hs.fidx.assign(d->face_vertex_ids, d->face_vertex_ids + 3 * (size_t)hs.nf);
   hs.fmat.assign(d->face_material_ids, d->face_material_ids + hs.nf);
   hs.mats.assign(d->materials, d->materials + d->n_materials);
@@ -133,49 +182,13 @@ extern "C" int rt_scene_create(const rt_mesh_desc* d, const rt_scene_opts* opts,
       return RT_ERR_INVALID;
     }
   }
-  // hoisted per-vertex / per-face invariants (same expressions as flyscene.cpp:449-450,459,574-577,599)
-  hs.wv.resize(hs.nv);
-  hs.vnn.resize(hs.nv);
-  hs.ov3.resize(3 * (size_t)hs.nv);
-  rt::parallel_for((size_t)hs.nv, [&](size_t b, size_t e) {
-    for (size_t i = b; i < e; i++) {
-      const float* v = d->vertices + 4 * i;
-      memcpy(&hs.ov3[3 * i], v, 12);
-      hs.wv[i] = rt::affv3(hs.M, f3{v[0] / v[3], v[1] / v[3], v[2] / v[3]});
-      const float* n = d->vertex_normals + 3 * i;
-      hs.vnn[i] = rt::normalized(f3{n[0], n[1], n[2]});
-    }
-  });
-  hs.fnn.resize(hs.nf);
-  hs.fdist.resize(hs.nf);
-  rt::parallel_for((size_t)hs.nf, [&](size_t b, size_t e) {
-    for (size_t f = b; f < e; f++) {
-      const float* n = d->face_normals + 3 * f;
-      hs.fnn[f] = rt::normalized(f3{n[0], n[1], n[2]});
-      hs.fdist[f] = rt::dot(hs.fnn[f], hs.wv[hs.fidx[3 * f]]);
-    }
-  });
-  rt::accept_region(hs);
+  rt::scene_invariants(hs, d);
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
   if (warm.t.joinable()) warm.t.join();
   s->prep_ms = ms_since(t0);
   auto t1 = clk::now();
-  bool boxes_done = false;
-  if (s->opts.box_builder == RT_BOXES_GPU && dev >= 0 && hs.nf > 0) {  // (a face-less scene: host)
-    bool nonfinite = false;
-    const int rc = rt::gpu_build_ref_boxes(dev, hs, d->vertices, s->opts.min_faces, s->opts.max_boxes,
-                                           &s->boxes_gpu_ms, &nonfinite);
-    if (rc) return rc;
-    if (!nonfinite) {
-      rt::PhaseTimer pr("boxes-gpu");
-      rt::assign_box_ranks(hs);
-      pr.mark("box_ranks");
-      boxes_done = true;
-      s->box_builder_used = RT_BOXES_GPU;
-    }
-  }
-  if (!boxes_done) rt::build_ref_boxes(hs, d->vertices, s->opts.min_faces, s->opts.max_boxes);
+  if (const int rc = rt::partition_ref_boxes(s.get(), dev, d->vertices)) return rc;
   s->boxes_ms = ms_since(t1);
   if (rt::debug_env("RT_TIMING"))
     fprintf(stderr, "[rt] boxes %.1f ms (%s, device %.1f ms), %zu boxes\n", s->boxes_ms,

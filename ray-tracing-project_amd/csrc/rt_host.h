@@ -81,6 +81,8 @@ inline Node64 wrap_single_leaf_root(const Aabb& box, float pad, uint32_t leaf) {
 // rt_refboxes.cpp
 void build_ref_boxes(HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes);
 void assign_box_ranks(HostScene& hs);  // face_rank / face_box from hs.boxes (creation order, in-box face order)
+// rt_host.cpp: the partition by the scene's box_builder (device `dev`, -1: host), ranks assigned
+int partition_ref_boxes(rt_scene* s, int dev, const float* v4);
 // rt_builders.cpp
 void build_bvh(HostScene& hs, int leaf_size, bool spatial);  // spatial: SBVH (RT_BUILDER_SBVH)
 // rt_layout.cpp

@@ -143,6 +143,29 @@ struct alignas(16) Node64 {
 };
 static_assert(sizeof(Node64) == 64, "node record must be 64 bytes");
 
+// Traversal-order hint of a node for waves whose rays share one direction octant (bit k of the octant:
+// axis k negative): bit `oct` set = visit child 1 first. Split-axis rule: along the axis on which the
+// children's centres are furthest apart, the child on the ray's entry side comes first. Only the visit
+// order depends on it, never a result (every needed child is still visited). Host (the re-layout, the host
+// refit) and device (k_refit_level) run this one function.
+RT_HD uint32_t octant_order(const Node64& nd) {
+  const float c0[3] = {nd.c0lx + nd.c0hx, nd.c0ly + nd.c0hy, nd.c0lz + nd.c0hz};
+  const float c1[3] = {nd.c1lx + nd.c1hx, nd.c1ly + nd.c1hy, nd.c1lz + nd.c1hz};
+  int axis = 0;
+  float best = -1.0f;
+  for (int k = 0; k < 3; k++) {
+    const float sep = fabsf(c1[k] - c0[k]);
+    if (sep > best) best = sep, axis = k;
+  }
+  const bool c1_low = c1[axis] < c0[axis];
+  uint32_t bits = 0;
+  for (uint32_t oct = 0; oct < 8; oct++) {
+    const bool negative = (oct >> axis) & 1u;
+    if (c1_low != negative) bits |= 1u << oct;
+  }
+  return bits;
+}
+
 // 4-wide node, one 64-B record: the four children's boxes quantised to 8 bits on a per-node grid
 // (origin + q * 2^e per axis, rounded outward -> conservative), plus the four child handles.
 struct alignas(16) Node4Q {

@@ -248,11 +248,49 @@ void tri_record(const HostScene& hs, uint32_t f, TriRec64& r, float Ro) {
   r.box = hs.face_box[f] | tri_flags(hs, f, Ro);
 }
 
-static void face_records(const HostScene& hs, std::vector<TriRec64>& out) {
+void face_records(const HostScene& hs, std::vector<TriRec64>& out) {
   out.resize(hs.nf);
   const float Ro = cert_origin_max(hs);
   parallel_chunks((size_t)hs.nf, [&](size_t b, size_t e, int) {
     for (size_t f = b; f < e; f++) tri_record(hs, (uint32_t)f, out[f], Ro);
+  });
+}
+
+// The device form of the binary node records (what device_upload sends and rt_debug_scene_records shows of a
+// host-only scene): pad0 / pad1 = the children's record offsets (prefetch targets; a leaf child: its first
+// triangle, behind the nodes) with the octant order bits in their low bits, interior children as byte offsets
+// of their records. out holds hs.nodes.size() records.
+void device_node_image(const HostScene& hs, Node64* out) {
+  const size_t nn = hs.nodes.size();
+  auto pf = [&](uint32_t c) -> uint32_t { return (uint32_t)(64 * (is_leaf(c) ? nn + leaf_first(c) : (size_t)c)); };
+  parallel_for(nn, [&](size_t b, size_t e) {
+    for (size_t i = b; i < e; i++) {
+      Node64 nd = hs.nodes[i];
+      const uint32_t order = nd.pad0;  // octant_order(), moved into the low offset bits
+      nd.pad0 = pf(nd.child0) | (order & 0x3Fu);
+      nd.pad1 = pf(nd.child1) | ((order >> 6) & 0x3u);
+      if (!is_leaf(nd.child0)) nd.child0 *= 64u;
+      if (!is_leaf(nd.child1)) nd.child1 *= 64u;
+      out[i] = nd;
+    }
+  });
+}
+
+// Per-slot shading record (float4 x 3), in the triangle records' (BVH leaf) order: the unit normals of the
+// slot's face's three vertices (Mesh normals as interpolateNormal normalises them, flyscene.cpp:599) and the
+// material id in the first .w. out holds 12 floats per slot of hs.tris.
+void device_fshade_image(const HostScene& hs, float* out) {
+  parallel_for(hs.tris.size(), [&](size_t b, size_t e) {
+    for (size_t sl = b; sl < e; sl++) {
+      const uint32_t f = hs.tris[sl].face;
+      float* r = out + 12 * sl;
+      for (int k = 0; k < 3; k++) {
+        const f3 n = hs.vnn[hs.fidx[3 * f + k]];
+        r[4 * k] = n.x; r[4 * k + 1] = n.y; r[4 * k + 2] = n.z; r[4 * k + 3] = 0.0f;
+      }
+      const int32_t m = hs.fmat[f];
+      memcpy(&r[3], &m, 4);
+    }
   });
 }
 
@@ -297,27 +335,7 @@ static void world_records(HostScene& hs) {
   });
 }
 
-// Traversal-order hint of a node for waves whose rays share one direction octant (bit k of the octant:
-// axis k negative): bit `oct` set = visit child 1 first. Split-axis rule: along the axis on which the
-// children's centres are furthest apart, the child on the ray's entry side comes first. Only the visit
-// order depends on it, never a result (every needed child is still visited).
-static uint32_t octant_order(const Node64& nd) {
-  const float c0[3] = {nd.c0lx + nd.c0hx, nd.c0ly + nd.c0hy, nd.c0lz + nd.c0hz};
-  const float c1[3] = {nd.c1lx + nd.c1hx, nd.c1ly + nd.c1hy, nd.c1lz + nd.c1hz};
-  int axis = 0;
-  float best = -1.0f;
-  for (int k = 0; k < 3; k++) {
-    const float sep = std::fabs(c1[k] - c0[k]);
-    if (sep > best) best = sep, axis = k;
-  }
-  const bool c1_low = c1[axis] < c0[axis];
-  uint32_t bits = 0;
-  for (uint32_t oct = 0; oct < 8; oct++) {
-    const bool negative = (oct >> axis) & 1u;
-    if (c1_low != negative) bits |= 1u << oct;
-  }
-  return bits;
-}
+// (a node's traversal-order hint: octant_order, rt_internal.h)
 
 // interior nodes re-laid out depth-first (near child first) from `root`; unreferenced nodes dropped;
 // sets hs.nodes, hs.root = 0, hs.depth (levels of interior nodes + the leaf level)

@@ -49,6 +49,33 @@ void ray_stream_release(rt_scene* s) {
   if (r.d_wf) (void)hipFree(r.d_wf);
   if (r.d_counts) (void)hipFree(r.d_counts);
   r = rt_scene::RayScratch{};
+  for (auto& u : s->list_use) {
+    (void)hipEventSynchronize((hipEvent_t)u.second);
+    (void)hipEventDestroy((hipEvent_t)u.second);
+  }
+  s->list_use.clear();
+}
+
+// A list call enqueued on a caller's stream reads the scene's records until its kernels end, whatever its flags
+// (an in-order list uses no scratch and records no scratch event): one event per caller stream, recorded after
+// each such call, for rt_scene_update to wait for (rt_refit.hip update_quiesce). Callers use a handful of streams;
+// beyond kListStreams the oldest entry's work is waited for and its event reused.
+constexpr size_t kListStreams = 64;
+static int note_list_use(rt_scene* s, hipStream_t st) {
+  void* ev = nullptr;
+  for (auto& u : s->list_use)
+    if (u.first == (void*)st) ev = u.second;
+  if (!ev && s->list_use.size() >= kListStreams) {
+    ev = s->list_use.front().second;
+    HIPCHECK(hipEventSynchronize((hipEvent_t)ev));
+    s->list_use.erase(s->list_use.begin());
+    s->list_use.emplace_back((void*)st, ev);
+  } else if (!ev) {
+    if (const int rc = rt::ensure_event(ev)) return rc;
+    s->list_use.emplace_back((void*)st, ev);
+  }
+  HIPCHECK(hipEventRecord((hipEvent_t)ev, st));
+  return RT_OK;
 }
 
 namespace {
@@ -475,7 +502,7 @@ extern "C" int rt_trace_stream(rt_scene* s, int32_t query, int32_t flags, const 
     if ((rc = check_device_pointer(s, q.p, "rt_trace_stream", q.what))) return rc;
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : (hipStream_t)s->stream;
   if ((rc = enqueue_rays(s, query, flags, R, lights, query == RT_RAYS_COLOR ? n_lights : 0, st))) return rc;
-  if (hip_stream) return RT_OK;
+  if (hip_stream) return note_list_use(s, st);
   HIPCHECK(hipStreamSynchronize(st));
   return check_prefetch_word(s);
 }
@@ -532,7 +559,7 @@ static int trace_stream_color(const char* who, rt_scene* s, int32_t flags, const
     rc = wavefront ? enqueue_wavefront(s, flags, R, P, st, lsrc) : enqueue_rays_depth(s, flags, R, P, st, lsrc);
   }
   if (rc) return rc;
-  if (hip_stream) return RT_OK;
+  if (hip_stream) return note_list_use(s, st);
   HIPCHECK(hipStreamSynchronize(st));
   return check_prefetch_word(s);
 }

@@ -96,6 +96,11 @@ void accept_region(HostScene& hs);
 inline const f3& bound_vert(const HostScene& hs, uint32_t f, int j) {
   return hs.av.empty() ? hs.wv[hs.fidx[3 * (size_t)f + j]] : hs.av[3 * (size_t)f + j];
 }
+// the device form of hs.nodes and the per-slot shading records (rt_layout.cpp)
+void device_node_image(const HostScene& hs, Node64* out);
+void device_fshade_image(const HostScene& hs, float* out);
+// exact-test records of every face, by face id (rt_layout.cpp)
+void face_records(const HostScene& hs, std::vector<TriRec64>& out);
 float scene_static_pad(const HostScene& hs);
 float cert_origin_max(const HostScene& hs);
 uint32_t tri_flags(const HostScene& hs, uint32_t f, float Ro);  // kSafeNormalBit | kBoxCertBit of face f
@@ -122,6 +127,22 @@ struct PhaseTimer {
     t = n;
   }
 };
+
+// What a refit needs of the tree's shape (rt_update.cpp refit_topology: one walk over hs.nodes from the root; the
+// shape never changes after rt_scene_create). `where` words are parent node * 2 + side.
+constexpr uint32_t kNoParent = 0xFFFFFFFFu;
+struct RefitTopo {
+  bool ready = false;
+  std::vector<uint32_t> leaf_handle, leaf_where;  // every leaf child but a single-leaf root's sentinel
+  std::vector<uint32_t> node_where;               // per node; kNoParent: the root, or not reachable from it
+  std::vector<uint32_t> level_nodes, level_off;   // reachable nodes by level: level_nodes[level_off[L] .. level_off[L + 1])
+};
+// the per-face words a device refit uploads (k_refit_slots puts them into the face's slots)
+struct FaceWords {
+  float nx, ny, nz, dist;
+  uint32_t rank, box;
+};
+static_assert(sizeof(FaceWords) == 24, "per-face upload record");
 
 }  // namespace rt
 
@@ -271,6 +292,9 @@ struct rt_scene {
     uint32_t* d_counts = nullptr;
     int32_t last_levels = -1;    // D of the last RT_RAYS_WAVEFRONT call (-1: none yet)
   } rays;
+  // List calls enqueued on caller streams (rt_trace_stream*, any flags): (stream, hipEvent_t recorded after the
+  // stream's latest such call). rt_scene_update waits for all of them; freed with the scene (rt_rays.hip).
+  std::vector<std::pair<void*, void*>> list_use;
   // View batches (rt_views.hip): the camera records of the latest rt_render_views call on the device, and the pinned
   // buffer they are uploaded from. Grown geometrically; a growth retires the old pair (freeing would wait for the
   // device), and everything is freed with the scene. ev_upload is recorded after each call's copy (the next call's
@@ -293,6 +317,22 @@ struct rt_scene {
   bool ray_bounds_valid = false;
   bool pending = false;
   std::vector<rt_light_set*> light_sets;  // the scene's live light sets (freed with the scene; rt_lights.hip)
+  // rt_scene_update (rt_update.cpp, rt_refit.hip): the tree's shape, and on the device (devices[0]) what is
+  // uploaded once at the first update -- the face indices, each leaf handle with its parent and side, each node's
+  // parent and side, the nodes grouped by level -- and the compact per-update arrays the kernels gather from.
+  // Freed with the scene (refit_release).
+  struct Refit {
+    rt::RefitTopo topo;
+    bool device_ready = false;
+    uint32_t *d_fidx = nullptr, *d_leaf_handle = nullptr, *d_leaf_where = nullptr, *d_node_where = nullptr,
+             *d_level_nodes = nullptr;
+    float *d_wv = nullptr, *d_vnn = nullptr, *d_av = nullptr, *d_slotbox = nullptr;
+    rt::FaceWords* d_face = nullptr;
+    int32_t* d_fmat = nullptr;
+  } refit;
+  // After a device refit the device holds the node boxes and the slot records; hs.nodes / hs.tris are refreshed
+  // from it by the first host reader (host_mirror)
+  bool host_stale = false;
 };
 
 namespace rt {
@@ -310,4 +350,22 @@ void ray_stream_release(rt_scene* s);  // rt_rays.hip; the scene's device is cur
 void view_batch_release(rt_scene* s);  // rt_views.hip; the scene's device is current
 // world bounds of the scene's vertices, computed at first use (rt_host.cpp)
 const float* scene_ray_bounds(rt_scene* s);
+// rt_scene_create's and rt_scene_update's per-vertex / per-face invariants from a mesh description whose
+// topology hs already holds (nv, nf, fidx): M / Minv / MS, wv, ov3, vnn, fnn, fdist, av (rt_host.cpp)
+void scene_invariants(HostScene& hs, const rt_mesh_desc* d);
+// ---- rt_scene_update ----
+void refit_topology(const HostScene& hs, RefitTopo& t);         // rt_update.cpp
+void refit_host(HostScene& hs, const RefitTopo& t, float pad);  // node boxes and order bits from bound_vert
+// rt_refit.hip (the scene's device is made current). update_quiesce: every frame slot stream of the scene and its
+// replicas drained, the ray and view scratch events waited for. device_refit: the slot records, shading records
+// and node boxes recomputed on devices[0] from `recs` (by face id) and hs; ms: upload, kernels (device events).
+// device_reupload: the same three from hs after a host refit. device_update_rest: reference boxes, materials,
+// the quantised tree (when replace4), the cached scalars and the replicas. host_mirror: hs.nodes / hs.tris
+// refreshed from the device when stale.
+int update_quiesce(rt_scene* s);
+int device_refit(rt_scene* s, const std::vector<TriRec64>& recs, float pad, double* upload_ms, double* refit_ms);
+int device_reupload(rt_scene* s);
+int device_update_rest(rt_scene* s, bool replace4, bool boxes_changed);
+int host_mirror(const rt_scene* s);
+void refit_release(rt_scene* s);
 }  // namespace rt

@@ -49,6 +49,7 @@ EXPORTS = [
     "rt_render_views", "rt_render_views_lit", "rt_debug_view_plan",
     "rt_sample_pattern_grid", "rt_sample_pattern_jittered", "rt_render_views_ss", "rt_render_views_ss_lit",
     "rt_render_ss", "rt_debug_sample_plan",
+    "rt_scene_update", "rt_debug_scene_records",
 ]
 RT_MAX_VIEWS = 65536
 RT_MAX_SAMPLES = 64
@@ -127,6 +128,15 @@ class SamplePattern(C.Structure):
     def array(self):
         """The offsets as float32 [n_samples, 2]."""
         return np.array([[o[0], o[1]] for o in self.offsets[:self.n_samples]], np.float32).reshape(-1, 2)
+
+
+class UpdateStats(C.Structure):
+    _fields_ = [("prep_ms", C.c_double), ("boxes_ms", C.c_double), ("records_ms", C.c_double),
+                ("upload_ms", C.c_double), ("refit_ms", C.c_double), ("total_ms", C.c_double),
+                ("bounds_on_device", C.c_int32), ("sah_cost", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class Frame(C.Structure):
@@ -257,6 +267,10 @@ def lib():
             L.rt_render_views_ss_lit.argtypes = [vp, C.POINTER(ViewBatch), vp, C.POINTER(Frame), SP, vp]
             L.rt_render_ss.argtypes = [vp, C.POINTER(Camera), vp, C.c_int32, C.POINTER(Frame), SP, vp]
             L.rt_debug_sample_plan.argtypes = [vp, C.c_int32, vp, C.c_int32]
+        # scene updates (builds from before them, loaded for A/B through RTAMD_LIB, lack these)
+        if hasattr(L, "rt_scene_update"):
+            L.rt_scene_update.argtypes = [vp, C.POINTER(MeshDesc), C.POINTER(UpdateStats)]
+            L.rt_debug_scene_records.argtypes = [vp, C.c_int32, C.c_int64, vp, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -413,6 +427,29 @@ class Scene:
             d.shape_model_matrix[:] = [float(x) for x in np.asarray(shape_model_matrix, np.float32).reshape(16)]
         o = scene_opts(device, min_faces, leaf_size, frames_in_flight, background, builder, box_builder, wide_tree, devices)
         check(lib().rt_scene_create(C.byref(d), C.byref(o), C.byref(self.h)))
+
+    def update(self, mesh, model_matrix=None, stats=False):
+        """rt_scene_update: the scene's geometry replaced by `mesh` (the same topology; vertices, normals, model
+        matrix and materials are read again). model_matrix: the desc's getShapeModelMatrix() override, e.g. the
+        matrix the scene was created with when a re-ingested mesh should not be re-normalised. Afterwards every
+        query gives the bits of a scene freshly created from the same description. stats: return the phase
+        times (rt_update_stats) as a dict."""
+        d = mesh.desc()
+        if model_matrix is not None:
+            d.shape_model_matrix[:] = [float(x) for x in np.asarray(model_matrix, np.float32).reshape(16)]
+        st = UpdateStats()
+        check(lib().rt_scene_update(self.h, C.byref(d), C.byref(st) if stats else None))
+        self.mesh = mesh
+        return st.as_dict() if stats else None
+
+    def records(self, which):
+        """rt_debug_scene_records: the device-form image of the binary nodes (0), the triangle records (1) or
+        the shading records (2), as bytes (uint8)."""
+        n = C.c_int64(0)
+        check(lib().rt_debug_scene_records(self.h, which, 0, None, C.byref(n)))
+        out = np.zeros(max(n.value, 1), np.uint8)
+        check(lib().rt_debug_scene_records(self.h, which, n.value, _p(out), C.byref(n)))
+        return out[: n.value]
 
     def info(self):
         i = SceneInfo()

@@ -187,6 +187,34 @@ static void view_batches(rt_scene* s) {
   rt_light_set_destroy(ls);
 }
 
+// rt_scene_update on the host-only scene: vertices moved twice and put back, the record images, and the refusals
+// (another face count, null arguments). Finite coordinates only: the reference's box partition, which create and
+// update both run, does not terminate for every placement of a NaN (tests/test_scene_update_host.py has a NaN step).
+static void scene_update(rt_scene* s, const rt_mesh_desc& d) {
+  std::vector<float> v(d.vertices, d.vertices + 4 * (size_t)d.n_vertices);
+  rt_mesh_desc moved = d;
+  moved.vertices = v.data();
+  rt_update_stats st;
+  int64_t info[7], n = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    for (size_t i = 0; i < v.size(); i += 4) v[i] += 0.01f * (float)((i / 4) % 7);
+    EXPECT(rt_scene_update(s, &moved, &st) == RT_OK && st.bounds_on_device == 0);
+    EXPECT(rt_debug_validate_bvh(s, info) == RT_OK);
+    for (int which = 0; which < 3; which++) {
+      EXPECT(rt_debug_scene_records(s, which, 0, nullptr, &n) == RT_OK);
+      std::vector<uint8_t> img((size_t)n + 1, 0xAB);
+      EXPECT(rt_debug_scene_records(s, which, n, img.data(), &n) == RT_OK && img[(size_t)n] == 0xAB);
+      EXPECT(n == 0 || rt_debug_scene_records(s, which, n - 1, img.data(), &n) == RT_ERR_INVALID);
+    }
+  }
+  EXPECT(rt_scene_update(s, &d, nullptr) == RT_OK);
+  rt_mesh_desc fewer = d;
+  fewer.n_faces = d.n_faces - 1;
+  EXPECT(rt_scene_update(s, &fewer, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_scene_update(s, nullptr, nullptr) == RT_ERR_INVALID && rt_scene_update(nullptr, &d, nullptr) == RT_ERR_INVALID);
+  EXPECT(rt_debug_scene_records(s, 3, 0, nullptr, &n) == RT_ERR_INVALID);
+}
+
 static void scene_roundtrip(const std::string& obj, int box_builder) {
   rt_mesh* m = nullptr;
   if (rt_mesh_load_obj(obj.c_str(), &m) != RT_OK) { std::fprintf(stderr, "skip %s\n", obj.c_str()); return; }
@@ -228,6 +256,7 @@ static void scene_roundtrip(const std::string& obj, int box_builder) {
   }
   light_sets(s);
   view_batches(s);
+  scene_update(s, d);
   rt_scene_destroy(s);  // frees the set light_sets() left alive
   rt_mesh_destroy(m);
 }
