@@ -57,12 +57,16 @@ $(VARLIB): $(PRODUCT_OBJS) $(OBJ)/rt_variants.o
 
 # A/B builds of the same sources with extra device flags (experiments only):
 #   make ablib TAG=noslp EXTRA="-fno-slp-vectorize"  ->  lib/librtamd_noslp.so  (select with RTAMD_LIB)
-# Every .hip that reaches the kernels of rt_kernels.h -- directly or through a header that includes it -- is rebuilt
-# with $(EXTRA) on every call (rt_variants.hip among them); the other objects are the product's.
+# Every .hip that reaches a traversal kernel -- a header that defines a __global__, directly or through other headers
+# -- is rebuilt with $(EXTRA) on every call (rt_variants.hip among them); the other objects are the product's.
+# KERNEL_HDRS: the headers that define a kernel, then (to a fixed point) every header that includes one of the set.
 empty :=
 space := $(empty) $(empty)
-KERNEL_HDRS := rt_kernels.h $(notdir $(shell grep -l 'include "rt_kernels.h"' $(PKG)/csrc/*.h))
-AB_NAMES  := $(basename $(notdir $(shell grep -lE 'include "($(subst $(space),|,$(KERNEL_HDRS)))"' $(PKG)/csrc/*.hip)))
+KERNEL_HDRS := $(shell cd $(PKG)/csrc && set=$$(grep -l '__global__' *.h) && while :; do \
+                 more=$$(grep -lE "include \"($$(echo $$set | tr ' ' '|'))\"" *.h); \
+                 new=$$(echo $$set $$more | tr ' ' '\n' | sort -u | tr '\n' ' '); \
+                 [ "$$new" = "$$set" ] && break; set=$$new; done; echo $$set)
+AB_NAMES  := $(basename $(notdir $(shell grep -lE 'include "($(subst $(space),|,$(strip $(KERNEL_HDRS))))"' $(PKG)/csrc/*.hip)))
 AB_OBJS   := $(AB_NAMES:%=$(OBJ)/%_$(TAG).o)
 AB_SHARED := $(filter-out $(AB_NAMES:%=$(OBJ)/%.o),$(PRODUCT_OBJS))
 $(AB_OBJS): $(OBJ)/%_$(TAG).o: $(PKG)/csrc/%.hip $(HDRS) FORCE
@@ -88,10 +92,12 @@ $(PKG)/lib/rt_render_cli: $(PKG)/host/main.cpp $(PKG)/host/flyscene.cpp $(PKG)/h
 oracle:
 	$(MAKE) -C oracle
 
-asm: $(PKG)/csrc/rt_frame.hip $(HDRS)
+# device assembly and resource usage of every source that instantiates traversal kernels (AB_NAMES):
+# build/asm/<source>.s and build/asm/<source>.resource.txt
+asm: $(AB_NAMES:%=$(OBJ)/asm/%.s)
+$(OBJ)/asm/%.s: $(PKG)/csrc/%.hip $(HDRS)
 	@mkdir -p $(OBJ)/asm
-	$(HIPCC) $(HIPFLAGS) --cuda-device-only -S -o $(OBJ)/asm/rt_frame.s $<
-	$(HIPCC) $(HIPFLAGS) --cuda-device-only -c -Rpass-analysis=kernel-resource-usage -o /dev/null $< 2> $(OBJ)/asm/resource.txt || true
+	$(HIPCC) $(HIPFLAGS) -Wno-unused-result --cuda-device-only -S -Rpass-analysis=kernel-resource-usage -o $@ $< 2> $(@:.s=.resource.txt)
 
 clean:
 	rm -rf $(OBJ) $(PKG)/lib

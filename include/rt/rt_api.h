@@ -507,7 +507,7 @@ int rt_debug_ray_order(rt_scene* s, int64_t capacity, uint32_t* perm_out, int64_
  *   max_depth   0 = the mode's own limit (PRIMARY 1, FULL 2); 1..RT_MAX_TRACE_DEPTH; else RT_ERR_INVALID.
  *   Ray i's colour, face and t are exactly what rt_render writes for a pixel whose camera ray is ray i, in that
  *   mode at that depth: a primary miss gives the scene's background, the material state stays with the chain
- *   from level to level and the final ks folds the levels, as in the frame kernel (csrc/rt_kernels.h
+ *   from level to level and the final ks folds the levels, as in the frame kernel (csrc/rt_trace_ray.h
  *   k_render_depth; the list kernel k_rays_depth runs a copy of its level loop).
  *   flags       RT_RAYS_REORDER, RT_RAYS_STATS as rt_trace_stream (the reorder groups level 0's rays).
  *               RT_RAYS_WAVEFRONT: trace level by level instead of chain by chain. Every level is a closest-hit
@@ -820,7 +820,7 @@ int rt_debug_timeline(rt_scene* s, int64_t capacity_waves, uint32_t* out8, int64
 /* Raw counters of the last RT_FRAME_STATS frame (diagnostics), out[0..n): 0 node visits, 1 triangle tests,
  * 2 wave node fetches, 3 wave triangle fetches, 4 primary rays, 5 hits, 6 total rays, 7 wave stack pops,
  * 8 pops at which no lane that wanted the entry still could reach it before its closest hit (closest-hit
- * traversal only); 48..63: the FULL kernel's packet walks by phase (csrc/rt_kernels.h ST_PW .. ST_PH); entries past
+ * traversal only); 48..63: the FULL kernel's packet walks by phase (csrc/rt_traverse.h ST_PW .. ST_PH); entries past
  * the last counter are 0. */
 int rt_debug_counters(rt_scene* s, int64_t n, int64_t* out);
 

@@ -24,16 +24,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "rt_scene.h"
-
-#define XCHECK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      rt::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return RT_ERR_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
+#include "rt_hip.h"
 
 namespace rt {
 namespace {
@@ -295,63 +286,45 @@ int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_
                         double* gpu_ms, bool* nonfinite_out) {
   const int nf = hs.nf;
   *nonfinite_out = false;
-  XCHECK(hipSetDevice(device));
+  HIPCHECK(hipSetDevice(device));
   PhaseTimer pt("boxes-gpu");
   hipStream_t st;
   st = (hipStream_t)build_stream(device);
   if (!st) return RT_ERR_HIP;
-  struct Guard {
-    hipStream_t st;
-    std::vector<void*> bufs;
-    std::vector<hipEvent_t> evs;
-    ~Guard() {
-      (void)hipStreamSynchronize(st);
-      for (void* b : bufs) (void)hipFree(b);
-      for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-  } g{st, {}, {}};
-  auto alloc = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) g.bufs.push_back(*p);
-    return e;
-  };
+  BuildScratch bs(st);
   float *d_v4 = nullptr, *d_fv = nullptr, *d_fvt = nullptr;
   uint32_t* d_fidx = nullptr;
   int32_t *d_ids = nullptr, *d_idt = nullptr, *d_flag = nullptr;
   DBox *d_boxes = nullptr, *d_child = nullptr;
-  XCHECK(alloc((void**)&d_v4, 16 * (size_t)hs.nv));
-  XCHECK(alloc((void**)&d_fidx, 12 * (size_t)nf));
-  XCHECK(alloc((void**)&d_fv, 36 * (size_t)nf));
-  XCHECK(alloc((void**)&d_fvt, 36 * (size_t)nf));
-  XCHECK(alloc((void**)&d_ids, 4 * (size_t)nf));
-  XCHECK(alloc((void**)&d_idt, 4 * (size_t)nf));
-  XCHECK(alloc((void**)&d_flag, 4));
+  HIPCHECK(bs.alloc(d_v4, 16 * (size_t)hs.nv));
+  HIPCHECK(bs.alloc(d_fidx, 12 * (size_t)nf));
+  HIPCHECK(bs.alloc(d_fv, 36 * (size_t)nf));
+  HIPCHECK(bs.alloc(d_fvt, 36 * (size_t)nf));
+  HIPCHECK(bs.alloc(d_ids, 4 * (size_t)nf));
+  HIPCHECK(bs.alloc(d_idt, 4 * (size_t)nf));
+  HIPCHECK(bs.alloc(d_flag, 4));
   // todo / child records of one pass: at most every box splits, and a pass can hold all boxes
   size_t cap = 1024;
-  XCHECK(alloc((void**)&d_boxes, cap * sizeof(DBox)));
-  XCHECK(alloc((void**)&d_child, cap * sizeof(DBox)));
-  hipEvent_t e0, e1;
-  XCHECK(hipEventCreate(&e0));
-  g.evs.push_back(e0);
-  XCHECK(hipEventCreate(&e1));
-  g.evs.push_back(e1);
+  HIPCHECK(bs.alloc(d_boxes, cap * sizeof(DBox)));
+  HIPCHECK(bs.alloc(d_child, cap * sizeof(DBox)));
+  HIPCHECK(bs.make_timer());
   pt.mark("alloc");
   // pageable sources through the pinned staging copies (h2d; a plain async copy from pageable memory runs
   // at ~1 GB/s)
   if (int rc = h2d(d_v4, v4, 16 * (size_t)hs.nv)) return rc;
   if (int rc = h2d(d_fidx, hs.fidx.data(), 12 * (size_t)nf)) return rc;
   pt.mark("h2d");
-  XCHECK(hipMemsetAsync(d_flag, 0, 4, st));
-  XCHECK(hipEventRecord(e0, st));
+  HIPCHECK(hipMemsetAsync(d_flag, 0, 4, st));
+  HIPCHECK(bs.start());
   hipLaunchKernelGGL(k_gather, dim3((nf + 255) / 256), dim3(256), 0, st, (const float*)d_v4, (const uint32_t*)d_fidx, nf,
                      d_fv, d_ids, d_flag);
   hipLaunchKernelGGL(k_fit_all, dim3(1), dim3(kBS), 0, st, (const float*)d_fv, nf, d_boxes);
-  XCHECK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
   int32_t flag = 0;
   std::vector<DBox> boxes(1);
-  XCHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-  XCHECK(hipMemcpyAsync(boxes.data(), d_boxes, sizeof(DBox), hipMemcpyDeviceToHost, st));
-  XCHECK(hipStreamSynchronize(st));
+  HIPCHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipMemcpyAsync(boxes.data(), d_boxes, sizeof(DBox), hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
   if (flag) { *nonfinite_out = true; return RT_OK; }
   // the passes of generateBoundingBoxes (flyscene.cpp:404-417)
   std::vector<DBox> todo, kids;
@@ -375,20 +348,20 @@ int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_
     notDone = true;
     if (todo.size() > cap) {
       while (cap < todo.size()) cap *= 2;
-      void *nb = nullptr, *nc = nullptr;
-      XCHECK(alloc(&nb, cap * sizeof(DBox)));
-      XCHECK(alloc(&nc, cap * sizeof(DBox)));
-      d_boxes = (DBox*)nb;
-      d_child = (DBox*)nc;
+      DBox *nb = nullptr, *nc = nullptr;
+      HIPCHECK(bs.alloc(nb, cap * sizeof(DBox)));
+      HIPCHECK(bs.alloc(nc, cap * sizeof(DBox)));
+      d_boxes = nb;
+      d_child = nc;
     }
     kids.resize(todo.size());
-    XCHECK(hipMemcpyAsync(d_boxes, todo.data(), todo.size() * sizeof(DBox), hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_boxes, todo.data(), todo.size() * sizeof(DBox), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_split_pass, dim3((unsigned)todo.size()), dim3(kBS), 0, st, d_boxes, d_child, d_fv, d_ids, d_fvt,
                        d_idt);
-    XCHECK(hipGetLastError());
-    XCHECK(hipMemcpyAsync(todo.data(), d_boxes, todo.size() * sizeof(DBox), hipMemcpyDeviceToHost, st));
-    XCHECK(hipMemcpyAsync(kids.data(), d_child, todo.size() * sizeof(DBox), hipMemcpyDeviceToHost, st));
-    XCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipMemcpyAsync(todo.data(), d_boxes, todo.size() * sizeof(DBox), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(kids.data(), d_child, todo.size() * sizeof(DBox), hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     if (timing) {
       const double now = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tp).count();
       int maxc = 0;
@@ -402,15 +375,13 @@ int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_
     for (size_t i = 0; i < todo.size(); i++)
       if (todo[i].result == 1) boxes.push_back(kids[i]);
   }
-  XCHECK(hipEventRecord(e1, st));
+  HIPCHECK(bs.stop());
   pt.mark("passes");
   std::vector<int32_t> ids(nf);
-  XCHECK(hipMemcpyAsync(ids.data(), d_ids, 4 * (size_t)nf, hipMemcpyDeviceToHost, st));
-  XCHECK(hipStreamSynchronize(st));
+  HIPCHECK(hipMemcpyAsync(ids.data(), d_ids, 4 * (size_t)nf, hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipStreamSynchronize(st));
   pt.mark("d2h_ids");
-  float ms = 0.0f;
-  XCHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (gpu_ms) *gpu_ms = ms;
+  HIPCHECK(bs.elapsed_ms(gpu_ms));
   hs.boxes.assign(boxes.size(), RefBox());
   for (size_t i = 0; i < boxes.size(); i++) {
     const DBox& d = boxes[i];

@@ -20,16 +20,7 @@
 #include <chrono>
 #include <vector>
 
-#include "rt_scene.h"
-
-#define BCHECK(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      rt::set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-      return RT_ERR_HIP;                                                                      \
-    }                                                                                         \
-  } while (0)
+#include "rt_hip.h"
 
 namespace rt {
 namespace {
@@ -295,62 +286,41 @@ int gpu_build_lbvh(int device, const std::vector<TriRec64>& face_recs, const flo
                    int leaf_size, float pad, std::vector<Node64>& nodes, std::vector<TriRec64>& tris, double* gpu_ms) {
   const int n = (int)face_recs.size();
   if (n < 2) { set_error("gpu_build_lbvh: needs at least 2 triangles"); return RT_ERR_INVALID; }
-  BCHECK(hipSetDevice(device));
+  HIPCHECK(hipSetDevice(device));
   hipStream_t st;
   st = (hipStream_t)build_stream(device);
   if (!st) return RT_ERR_HIP;
-  struct Guard {
-    hipStream_t st;
-    std::vector<void*> bufs;
-    std::vector<hipEvent_t> evs;  // released on every return (the fallback paths included)
-    ~Guard() {
-      (void)hipStreamSynchronize(st);
-      for (void* b : bufs) (void)hipFree(b);
-      for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-  } g{st, {}, {}};
-  auto alloc = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) g.bufs.push_back(*p);
-    return e;
-  };
+  BuildScratch bs(st);  // released on every return (the fallback paths included)
   TriRec64 *d_rec = nullptr, *d_tris = nullptr;
   uint64_t *d_k0 = nullptr, *d_k1 = nullptr;
   int2 *d_range = nullptr, *d_child = nullptr;
   int *d_pint = nullptr, *d_pleaf = nullptr, *d_flags = nullptr;
   Box6 *d_pbox = nullptr, *d_nbox = nullptr;
   Node64* d_nodes = nullptr;
-  BCHECK(alloc((void**)&d_rec, (size_t)n * sizeof(TriRec64)));
-  BCHECK(alloc((void**)&d_tris, (size_t)n * sizeof(TriRec64)));
-  BCHECK(alloc((void**)&d_k0, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_k1, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_range, (size_t)n * sizeof(int2)));
-  BCHECK(alloc((void**)&d_child, (size_t)n * sizeof(int2)));
-  BCHECK(alloc((void**)&d_pint, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_pleaf, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_flags, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_pbox, (size_t)n * sizeof(Box6)));
-  BCHECK(alloc((void**)&d_nbox, (size_t)n * sizeof(Box6)));
-  BCHECK(alloc((void**)&d_nodes, (size_t)n * sizeof(Node64)));
+  HIPCHECK(bs.alloc(d_rec, (size_t)n * sizeof(TriRec64)));
+  HIPCHECK(bs.alloc(d_tris, (size_t)n * sizeof(TriRec64)));
+  HIPCHECK(bs.alloc(d_k0, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_k1, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_range, (size_t)n * sizeof(int2)));
+  HIPCHECK(bs.alloc(d_child, (size_t)n * sizeof(int2)));
+  HIPCHECK(bs.alloc(d_pint, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_pleaf, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_flags, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_pbox, (size_t)n * sizeof(Box6)));
+  HIPCHECK(bs.alloc(d_nbox, (size_t)n * sizeof(Box6)));
+  HIPCHECK(bs.alloc(d_nodes, (size_t)n * sizeof(Node64)));
   if (int rc = h2d(d_rec, face_recs.data(), (size_t)n * sizeof(TriRec64))) return rc;  // pinned staging
-  BCHECK(hipMemsetAsync(d_flags, 0, (size_t)n * 4, st));
-  hipEvent_t e0, e1;
-  BCHECK(hipEventCreate(&e0));
-  g.evs.push_back(e0);
-  BCHECK(hipEventCreate(&e1));
-  g.evs.push_back(e1);
-  BCHECK(hipEventRecord(e0, st));
+  HIPCHECK(hipMemsetAsync(d_flags, 0, (size_t)n * 4, st));
+  HIPCHECK(bs.make_timer());
+  HIPCHECK(bs.start());
   const int B = 256, G = (n + B - 1) / B;
-  float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc;
-  fsc.x = hi[0] > lo[0] ? 1024.0f / (hi[0] - lo[0]) : 0.0f;
-  fsc.y = hi[1] > lo[1] ? 1024.0f / (hi[1] - lo[1]) : 0.0f;
-  fsc.z = hi[2] > lo[2] ? 1024.0f / (hi[2] - lo[2]) : 0.0f;
+  const float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc = morton_scale(lo, hi);
   hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, st, (const TriRec64*)d_rec, n, flo, fsc, d_k0);
   size_t tb = 0;
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
   void* d_tmp = nullptr;
-  BCHECK(alloc(&d_tmp, tb));
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(bs.alloc(d_tmp, tb));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
   hipLaunchKernelGGL(k_karras, dim3(G), dim3(B), 0, st, (const uint64_t*)d_k1, n, d_range, d_child, d_pint, d_pleaf);
   hipLaunchKernelGGL(k_leaf_boxes, dim3(G), dim3(B), 0, st, (const uint64_t*)d_k1, (const TriRec64*)d_rec, n, d_pbox);
   hipLaunchKernelGGL(k_bottom_up, dim3(G), dim3(B), 0, st, (const int2*)d_child, (const int*)d_pint, (const int*)d_pleaf,
@@ -358,16 +328,14 @@ int gpu_build_lbvh(int device, const std::vector<TriRec64>& face_recs, const flo
   hipLaunchKernelGGL(k_emit_nodes, dim3(G), dim3(B), 0, st, (const int2*)d_child, (const int2*)d_range,
                      (const Box6*)d_pbox, (const Box6*)d_nbox, d_nodes, n, leaf_size, pad);
   hipLaunchKernelGGL(k_emit_tris, dim3(G), dim3(B), 0, st, (const uint64_t*)d_k1, (const TriRec64*)d_rec, d_tris, n);
-  BCHECK(hipGetLastError());
-  BCHECK(hipEventRecord(e1, st));
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(bs.stop());
   nodes.resize((size_t)n - 1);
   tris.resize(n);
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHECK(hipStreamSynchronize(st));
   if (int rc = d2h(nodes.data(), d_nodes, (size_t)(n - 1) * sizeof(Node64))) return rc;  // pinned staging
   if (int rc = d2h(tris.data(), d_tris, (size_t)n * sizeof(TriRec64))) return rc;
-  float ms = 0.0f;
-  BCHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (gpu_ms) *gpu_ms = ms;
+  HIPCHECK(bs.elapsed_ms(gpu_ms));
   return RT_OK;
 }
 
@@ -381,25 +349,11 @@ int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const flo
   const int n = (int)face_recs.size();
   if (n < 2) { set_error("gpu_build_ploc: needs at least 2 triangles"); return RT_ERR_INVALID; }
   radius = std::max(1, std::min(radius, kPlocMaxRadius));
-  BCHECK(hipSetDevice(device));
+  HIPCHECK(hipSetDevice(device));
   hipStream_t st;
   st = (hipStream_t)build_stream(device);
   if (!st) return RT_ERR_HIP;
-  struct Guard {
-    hipStream_t st;
-    std::vector<void*> bufs;
-    std::vector<hipEvent_t> evs;  // released on every return (the fallback paths included)
-    ~Guard() {
-      (void)hipStreamSynchronize(st);
-      for (void* b : bufs) (void)hipFree(b);
-      for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-  } g{st, {}, {}};
-  auto alloc = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) g.bufs.push_back(*p);
-    return e;
-  };
+  BuildScratch bs(st);  // released on every return (the fallback paths included)
   TriRec64* d_rec = nullptr;
   uint64_t *d_k0 = nullptr, *d_k1 = nullptr, *d_flags = nullptr, *d_pos = nullptr;
   Cluster *d_ca = nullptr, *d_cb = nullptr;
@@ -408,60 +362,53 @@ int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const flo
   int *d_nn = nullptr, *d_pint = nullptr, *d_pleaf = nullptr, *d_cflags = nullptr, *d_count = nullptr;
   float* d_cost = nullptr;
   uint8_t* d_leaf = nullptr;
-  BCHECK(alloc((void**)&d_rec, (size_t)n * sizeof(TriRec64)));
-  BCHECK(alloc((void**)&d_k0, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_k1, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_flags, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_pos, (size_t)n * 8));
-  BCHECK(alloc((void**)&d_ca, (size_t)n * sizeof(Cluster)));
-  BCHECK(alloc((void**)&d_cb, (size_t)n * sizeof(Cluster)));
-  BCHECK(alloc((void**)&d_tbox, (size_t)n * sizeof(Box6)));
-  BCHECK(alloc((void**)&d_nbox, (size_t)n * sizeof(Box6)));
-  BCHECK(alloc((void**)&d_child, (size_t)n * sizeof(int2)));
-  BCHECK(alloc((void**)&d_nn, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_pint, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_pleaf, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_cflags, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_count, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_cost, (size_t)n * 4));
-  BCHECK(alloc((void**)&d_leaf, (size_t)n));
+  HIPCHECK(bs.alloc(d_rec, (size_t)n * sizeof(TriRec64)));
+  HIPCHECK(bs.alloc(d_k0, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_k1, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_flags, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_pos, (size_t)n * 8));
+  HIPCHECK(bs.alloc(d_ca, (size_t)n * sizeof(Cluster)));
+  HIPCHECK(bs.alloc(d_cb, (size_t)n * sizeof(Cluster)));
+  HIPCHECK(bs.alloc(d_tbox, (size_t)n * sizeof(Box6)));
+  HIPCHECK(bs.alloc(d_nbox, (size_t)n * sizeof(Box6)));
+  HIPCHECK(bs.alloc(d_child, (size_t)n * sizeof(int2)));
+  HIPCHECK(bs.alloc(d_nn, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_pint, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_pleaf, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_cflags, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_count, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_cost, (size_t)n * 4));
+  HIPCHECK(bs.alloc(d_leaf, (size_t)n));
   if (int rc = h2d(d_rec, face_recs.data(), (size_t)n * sizeof(TriRec64))) return rc;  // pinned staging
-  BCHECK(hipMemsetAsync(d_pint, 0xFF, (size_t)n * 4, st));  // the root's parent: -1
-  BCHECK(hipMemsetAsync(d_cflags, 0, (size_t)n * 4, st));
-  hipEvent_t e0, e1;
-  BCHECK(hipEventCreate(&e0));
-  g.evs.push_back(e0);
-  BCHECK(hipEventCreate(&e1));
-  g.evs.push_back(e1);
-  BCHECK(hipEventRecord(e0, st));
+  HIPCHECK(hipMemsetAsync(d_pint, 0xFF, (size_t)n * 4, st));  // the root's parent: -1
+  HIPCHECK(hipMemsetAsync(d_cflags, 0, (size_t)n * 4, st));
+  HIPCHECK(bs.make_timer());
+  HIPCHECK(bs.start());
   const int B = 256, G = (n + B - 1) / B;
-  float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc;
-  fsc.x = hi[0] > lo[0] ? 1024.0f / (hi[0] - lo[0]) : 0.0f;
-  fsc.y = hi[1] > lo[1] ? 1024.0f / (hi[1] - lo[1]) : 0.0f;
-  fsc.z = hi[2] > lo[2] ? 1024.0f / (hi[2] - lo[2]) : 0.0f;
+  const float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc = morton_scale(lo, hi);
   hipLaunchKernelGGL(k_morton, dim3(G), dim3(B), 0, st, (const TriRec64*)d_rec, n, flo, fsc, d_k0);
   size_t tb = 0, tscan = 0;
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
-  BCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tscan, d_flags, d_pos, n, st));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tscan, d_flags, d_pos, n, st));
   void* d_tmp = nullptr;
-  BCHECK(alloc(&d_tmp, std::max(tb, tscan)));
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(bs.alloc(d_tmp, std::max(tb, tscan)));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
   hipLaunchKernelGGL(k_ploc_init, dim3(G), dim3(B), 0, st, (const uint64_t*)d_k1, (const TriRec64*)d_rec, n, d_ca, d_tbox);
-  BCHECK(hipGetLastError());
+  HIPCHECK(hipGetLastError());
   int N = n, base = 0, iters = 0;
   Cluster *cur = d_ca, *nxt = d_cb;
   while (N > 1) {
     const int g = (N + kPlocBlock - 1) / kPlocBlock;
     hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(kPlocBlock), 0, st, (const Cluster*)cur, N, radius, d_nn);
     hipLaunchKernelGGL(k_ploc_flags, dim3(g), dim3(kPlocBlock), 0, st, (const int*)d_nn, N, d_flags);
-    BCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tscan, d_flags, d_pos, N, st));
+    HIPCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, tscan, d_flags, d_pos, N, st));
     hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(kPlocBlock), 0, st, (const Cluster*)cur, (const int*)d_nn,
                        (const uint64_t*)d_flags, (const uint64_t*)d_pos, N, base, nxt, d_child, d_nbox, d_pint, d_pleaf);
-    BCHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     uint64_t tail[2];
-    BCHECK(hipMemcpyAsync(&tail[0], d_pos + (N - 1), 8, hipMemcpyDeviceToHost, st));
-    BCHECK(hipMemcpyAsync(&tail[1], d_flags + (N - 1), 8, hipMemcpyDeviceToHost, st));
-    BCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipMemcpyAsync(&tail[0], d_pos + (N - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&tail[1], d_flags + (N - 1), 8, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     const uint64_t tot = tail[0] + tail[1];
     const int merges = (int)(tot >> 32), keeps = (int)(tot & 0xFFFFFFFFull);
     if (merges == 0 || keeps != N - merges) { set_error("gpu_build_ploc: clustering stalled (non-finite boxes?)"); return RT_ERR_INVALID; }
@@ -474,18 +421,16 @@ int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const flo
   hipLaunchKernelGGL(k_ploc_collapse, dim3(G), dim3(B), 0, st, (const int2*)d_child, (const int*)d_pint,
                      (const int*)d_pleaf, (const Box6*)d_nbox, (const Box6*)d_tbox, d_cflags, d_count, d_cost, d_leaf, n,
                      std::max(1, std::min(leaf_size, kMaxLeaf)), k_trav, rule);
-  BCHECK(hipGetLastError());
-  BCHECK(hipEventRecord(e1, st));
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(bs.stop());
   child2.resize(2 * (size_t)(n - 1));
   box6.resize(6 * (size_t)(n - 1));
   leaf.resize((size_t)(n - 1));
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHECK(hipStreamSynchronize(st));
   if (int rc = d2h(child2.data(), d_child, (size_t)(n - 1) * sizeof(int2))) return rc;  // pinned staging
   if (int rc = d2h(box6.data(), d_nbox, (size_t)(n - 1) * sizeof(Box6))) return rc;
   if (int rc = d2h(leaf.data(), d_leaf, (size_t)(n - 1))) return rc;
-  float ms = 0.0f;
-  BCHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (gpu_ms) *gpu_ms = ms;
+  HIPCHECK(bs.elapsed_ms(gpu_ms));
   if (iterations) *iterations = iters;
   return RT_OK;
 }
@@ -1045,26 +990,12 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
   const size_t N = (size_t)n;
   const size_t cap = std::min<size_t>(spatial ? N + (size_t)(budget * (double)N) + 1 : N, (size_t)kMaxFaces);
   if (cap < N) { set_error("gpu_build_sah: too many faces"); return RT_ERR_INVALID; }
-  BCHECK(hipSetDevice(device));
+  HIPCHECK(hipSetDevice(device));
   PhaseTimer pt("gpu_build_sah");
   hipStream_t st;
   st = (hipStream_t)build_stream(device);
   if (!st) return RT_ERR_HIP;
-  struct Guard {
-    hipStream_t st;
-    std::vector<void*> bufs;
-    std::vector<hipEvent_t> evs;  // released on every return (the fallback paths included)
-    ~Guard() {
-      (void)hipStreamSynchronize(st);
-      for (void* b : bufs) (void)hipFree(b);
-      for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-    }
-  } g{st, {}, {}};
-  auto alloc = [&](void** p, size_t bytes) -> hipError_t {
-    hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e == hipSuccess) g.bufs.push_back(*p);
-    return e;
-  };
+  BuildScratch bs(st);  // released on every return (the fallback paths included)
   const size_t maxbig = cap / kSahSmall + 2, objw = 3 * kSahBins * kObjW, spw = 3 * kSahBins * kSpW;
   TriRec64* d_rec = nullptr;
   uint64_t *d_k0 = nullptr, *d_k1 = nullptr, *d_lr = nullptr, *d_slr = nullptr;
@@ -1074,49 +1005,42 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
   int32_t* d_pt[2] = {nullptr, nullptr};
   SahTask* d_task[2] = {nullptr, nullptr};
   uint8_t* d_side = nullptr;
-  BCHECK(alloc((void**)&d_rec, N * sizeof(TriRec64)));
-  BCHECK(alloc((void**)&d_k0, N * 8));
-  BCHECK(alloc((void**)&d_k1, N * 8));
-  BCHECK(alloc((void**)&d_ncb, 2 * cap * sizeof(Box6)));
-  BCHECK(alloc((void**)&d_nchild, 2 * cap * 4));
+  HIPCHECK(bs.alloc(d_rec, N * sizeof(TriRec64)));
+  HIPCHECK(bs.alloc(d_k0, N * 8));
+  HIPCHECK(bs.alloc(d_k1, N * 8));
+  HIPCHECK(bs.alloc(d_ncb, 2 * cap * sizeof(Box6)));
+  HIPCHECK(bs.alloc(d_nchild, 2 * cap * 4));
   for (int q = 0; q < 2; q++) {
-    BCHECK(alloc((void**)&d_rface[q], cap * 4));
-    BCHECK(alloc((void**)&d_rbox[q], cap * sizeof(Box6)));
-    BCHECK(alloc((void**)&d_pt[q], cap * 4));
-    BCHECK(alloc((void**)&d_task[q], cap * sizeof(SahTask)));
+    HIPCHECK(bs.alloc(d_rface[q], cap * 4));
+    HIPCHECK(bs.alloc(d_rbox[q], cap * sizeof(Box6)));
+    HIPCHECK(bs.alloc(d_pt[q], cap * 4));
+    HIPCHECK(bs.alloc(d_task[q], cap * sizeof(SahTask)));
   }
-  BCHECK(alloc((void**)&d_stat, cap * 12 * 4));
-  BCHECK(alloc((void**)&d_bins, maxbig * objw * 4));
-  if (spatial) BCHECK(alloc((void**)&d_spbins, maxbig * spw * 4));
-  BCHECK(alloc((void**)&d_lr, (cap + 1) * 8));
-  BCHECK(alloc((void**)&d_slr, (cap + 1) * 8));
-  BCHECK(alloc((void**)&d_fin, (cap + 1) * 4));
-  BCHECK(alloc((void**)&d_sfin, (cap + 1) * 4));
-  BCHECK(alloc((void**)&d_side, cap));
-  BCHECK(alloc((void**)&d_cnt, 32));
+  HIPCHECK(bs.alloc(d_stat, cap * 12 * 4));
+  HIPCHECK(bs.alloc(d_bins, maxbig * objw * 4));
+  if (spatial) HIPCHECK(bs.alloc(d_spbins, maxbig * spw * 4));
+  HIPCHECK(bs.alloc(d_lr, (cap + 1) * 8));
+  HIPCHECK(bs.alloc(d_slr, (cap + 1) * 8));
+  HIPCHECK(bs.alloc(d_fin, (cap + 1) * 4));
+  HIPCHECK(bs.alloc(d_sfin, (cap + 1) * 4));
+  HIPCHECK(bs.alloc(d_side, cap));
+  HIPCHECK(bs.alloc(d_cnt, 32));
   pt.mark("alloc");
   if (int rc = h2d(d_rec, face_recs.data(), N * sizeof(TriRec64))) return rc;  // pinned staging
   pt.mark("h2d_records");
-  hipEvent_t e0, e1;
-  BCHECK(hipEventCreate(&e0));
-  g.evs.push_back(e0);
-  BCHECK(hipEventCreate(&e1));
-  g.evs.push_back(e1);
-  BCHECK(hipEventRecord(e0, st));
+  HIPCHECK(bs.make_timer());
+  HIPCHECK(bs.start());
   const int B = kSahBlock;
   auto grid = [&](size_t k) { return dim3((unsigned)((k + B - 1) / B)); };
-  float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc;
-  fsc.x = hi[0] > lo[0] ? 1024.0f / (hi[0] - lo[0]) : 0.0f;
-  fsc.y = hi[1] > lo[1] ? 1024.0f / (hi[1] - lo[1]) : 0.0f;
-  fsc.z = hi[2] > lo[2] ? 1024.0f / (hi[2] - lo[2]) : 0.0f;
+  const float3 flo = make_float3(lo[0], lo[1], lo[2]), fsc = morton_scale(lo, hi);
   hipLaunchKernelGGL(k_morton, grid(N), dim3(B), 0, st, (const TriRec64*)d_rec, n, flo, fsc, d_k0);
   size_t tb = 0, ts1 = 0, ts2 = 0;
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
-  BCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, ts1, d_lr, d_slr, (int)(cap + 1), st));
-  BCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, ts2, d_fin, d_sfin, (int)(cap + 1), st));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(nullptr, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, ts1, d_lr, d_slr, (int)(cap + 1), st));
+  HIPCHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, ts2, d_fin, d_sfin, (int)(cap + 1), st));
   void* d_tmp = nullptr;
-  BCHECK(alloc(&d_tmp, std::max(tb, std::max(ts1, ts2))));
-  BCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
+  HIPCHECK(bs.alloc(d_tmp, std::max(tb, std::max(ts1, ts2))));
+  HIPCHECK(hipcub::DeviceRadixSort::SortKeys(d_tmp, tb, d_k0, d_k1, n, 0, 64, st));
   hipLaunchKernelGGL(k_sah_init, grid(N), dim3(B), 0, st, (const uint64_t*)d_k1, (const TriRec64*)d_rec, n, d_rface[0],
                      d_rbox[0], d_pt[0]);
   SahTask root{};
@@ -1128,7 +1052,7 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
   root.child = -1;
   root.axis = root.bin = -1;
   root.budget = (int32_t)(cap - N);
-  BCHECK(hipMemcpyAsync(d_task[0], &root, sizeof root, hipMemcpyHostToDevice, st));
+  HIPCHECK(hipMemcpyAsync(d_task[0], &root, sizeof root, hipMemcpyHostToDevice, st));
   float root_area;
   {
     const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
@@ -1141,7 +1065,7 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
     if (level > 4 * kMaxDepth) { set_error("gpu_build_sah: no progress"); return RT_ERR_INVALID; }
     const int force = level >= kMaxDepth - 20 ? 1 : 0;
     uint32_t cinit[8] = {0, nodes, 0, 0, leaves, 0, 0, 0};
-    BCHECK(hipMemcpyAsync(d_cnt, cinit, 32, hipMemcpyHostToDevice, st));
+    HIPCHECK(hipMemcpyAsync(d_cnt, cinit, 32, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_sah_stat_init, grid(ntask), dim3(B), 0, st, d_stat, ntask);
     if (nbig)
       hipLaunchKernelGGL(k_sah_bins_init, grid((size_t)nbig * 3 * kSahBins), dim3(B), 0, st, d_bins, nbig * 3 * kSahBins, kObjW);
@@ -1153,8 +1077,8 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
                        (const uint32_t*)d_bins, d_cnt, root_area, alpha, spatial ? 1 : 0, force);
     if (spatial && nbig) {
       uint32_t nsp = 0;
-      BCHECK(hipMemcpyAsync(&nsp, d_cnt + 3, 4, hipMemcpyDeviceToHost, st));
-      BCHECK(hipStreamSynchronize(st));
+      HIPCHECK(hipMemcpyAsync(&nsp, d_cnt + 3, 4, hipMemcpyDeviceToHost, st));
+      HIPCHECK(hipStreamSynchronize(st));
       if (nsp > maxbig) { set_error("gpu_build_sah: spatial task bound exceeded"); return RT_ERR_INVALID; }
       if (nsp) {
         hipLaunchKernelGGL(k_sah_bins_init, grid((size_t)nsp * 3 * kSahBins), dim3(B), 0, st, d_spbins, (int)nsp * 3 * kSahBins, kSpW);
@@ -1169,25 +1093,25 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
     hipLaunchKernelGGL(k_sah_side, grid(m + 1), dim3(B), 0, st, (const uint32_t*)d_rface[cur], (const Box6*)d_rbox[cur],
                        (const int32_t*)d_pt[cur], (const SahTask*)d_task[cur], (const uint32_t*)d_stat,
                        (const TriRec64*)d_rec, (const uint8_t*)d_side, (int)m, d_lr, d_fin);
-    BCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, ts1, d_lr, d_slr, (int)(m + 1), st));
-    BCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, ts2, d_fin, d_sfin, (int)(m + 1), st));
+    HIPCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, ts1, d_lr, d_slr, (int)(m + 1), st));
+    HIPCHECK(hipcub::DeviceScan::ExclusiveSum(d_tmp, ts2, d_fin, d_sfin, (int)(m + 1), st));
     hipLaunchKernelGGL(k_sah_fix, grid(ntask), dim3(B), 0, st, (const SahTask*)d_task[cur], ntask, (const uint64_t*)d_slr,
                        (const uint32_t*)d_sfin, d_task[1 - cur], d_cnt);
     uint64_t slr_m = 0;
     uint32_t sfin_m = 0;
-    BCHECK(hipMemcpyAsync(&slr_m, d_slr + m, 8, hipMemcpyDeviceToHost, st));
-    BCHECK(hipMemcpyAsync(&sfin_m, d_sfin + m, 4, hipMemcpyDeviceToHost, st));
-    BCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipMemcpyAsync(&slr_m, d_slr + m, 8, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipMemcpyAsync(&sfin_m, d_sfin + m, 4, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     const uint32_t m_next = sfin_m + (uint32_t)(slr_m >> 32) + (uint32_t)slr_m;
     if (m_next > cap || m_next < m) { set_error("gpu_build_sah: reference bound exceeded"); return RT_ERR_INVALID; }
     hipLaunchKernelGGL(k_sah_scatter, grid(m), dim3(B), 0, st, (const uint32_t*)d_rface[cur], (const Box6*)d_rbox[cur],
                        (const int32_t*)d_pt[cur], (const SahTask*)d_task[cur], (const TriRec64*)d_rec,
                        (const uint64_t*)d_slr, (const uint32_t*)d_sfin, (int)m, d_rface[1 - cur], d_rbox[1 - cur],
                        d_pt[1 - cur]);
-    BCHECK(hipGetLastError());
+    HIPCHECK(hipGetLastError());
     uint32_t cnt[8];
-    BCHECK(hipMemcpyAsync(cnt, d_cnt, 32, hipMemcpyDeviceToHost, st));
-    BCHECK(hipStreamSynchronize(st));
+    HIPCHECK(hipMemcpyAsync(cnt, d_cnt, 32, hipMemcpyDeviceToHost, st));
+    HIPCHECK(hipStreamSynchronize(st));
     ntask = (int)cnt[0];
     nodes = cnt[1];
     nbig = (int)cnt[2];
@@ -1197,21 +1121,19 @@ int gpu_build_sah(int device, const std::vector<TriRec64>& face_recs, const floa
     cur = 1 - cur;
     level++;
   }
-  BCHECK(hipEventRecord(e1, st));
+  HIPCHECK(bs.stop());
   std::vector<int32_t> ptag(m);
   nchild.resize(2 * (size_t)nodes);
   ncb.resize(12 * (size_t)nodes);
   slot_face.resize(m);
-  BCHECK(hipStreamSynchronize(st));
+  HIPCHECK(hipStreamSynchronize(st));
   pt.mark("levels");
   if (int rc = d2h(nchild.data(), d_nchild, 2 * (size_t)nodes * 4)) return rc;  // pinned staging
   if (int rc = d2h(ncb.data(), d_ncb, 2 * (size_t)nodes * sizeof(Box6))) return rc;
   if (int rc = d2h(slot_face.data(), d_rface[cur], (size_t)m * 4)) return rc;
   if (int rc = d2h(ptag.data(), d_pt[cur], (size_t)m * 4)) return rc;
   pt.mark("d2h");
-  float ms = 0.0f;
-  BCHECK(hipEventElapsedTime(&ms, e0, e1));
-  if (gpu_ms) *gpu_ms = ms;
+  HIPCHECK(bs.elapsed_ms(gpu_ms));
   if (levels) *levels = level;
   // leaves: each leaf id's references are one contiguous run of the final order
   std::vector<uint32_t> first(leaves, UINT32_MAX), count(leaves, 0);

@@ -3,8 +3,10 @@
 // the small rules every stage repeats (drain a scene's slots, create an event at first use, regrow a slot's
 // buffer). Private to those files: no host .cpp includes it (rt_scene.h carries what the host side needs).
 #pragma once
+#include <cstring>
+
 #include "rt_dispatch.h"
-#include "rt_kernels.h"
+#include "rt_hip.h"
 
 namespace rt {
 

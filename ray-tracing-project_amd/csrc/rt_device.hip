@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_traverse.h"  // kStatSlots
 
 namespace rt {
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_traverse.h"  // ballot, lane_id
 
 namespace rt {
 

@@ -1,12 +1,15 @@
 // rt_frame.hip -- the single-device frame path of the MI355X ray-traversal library: a frame's parameters, the
 // longest-first dispatch order (k_order_lpt), the frame buffers, the box-colour table, the launch of the kernel the
-// plan names (rt_dispatch.h plan_frame), and the wait for it; rt_render* and the debug readers. The device code of
-// the hot path is rt_kernels.h (shared with the A/B variants of rt_variants.hip): this is the one product
-// translation unit that instantiates its frame kernels, and it holds the weak default of variant_launch.
+// plan names (rt_dispatch.h plan_frame), and the wait for it; rt_render* and the debug readers. The frame
+// kernels are rt_frame_kernels.h (with k_render_depth of rt_trace_ray.h; shared with the A/B variants of
+// rt_variants.hip): this is the one product translation unit that instantiates them, and it holds the weak default
+// of variant_launch (rt_variant_api.h).
 #include <atomic>
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_frame_kernels.h"
+#include "rt_variant_api.h"
 
 namespace rt {
 

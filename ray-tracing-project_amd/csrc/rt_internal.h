@@ -313,7 +313,7 @@ struct FrameParams {
   uint32_t* cost_dil;
   int32_t dil_r;
   // pred: each wave raises cost_dil around the wave where its primary hit point is expected in the next frame
-  // instead of around itself (rt_kernels.h pred_mark / wave_clock_end): pred_proj = (a, b, c, e), a pixel's
+  // instead of around itself (rt_frame_wave.h wave_clock_end): pred_proj = (a, b, c, e), a pixel's
   // view-space ray direction (a px + b, c py + e, -1); pred_step = the camera's last step as a view-space
   // translation (V_n V_(n-1)^-1), applied once more; 0 = off
   int32_t pred;
@@ -327,7 +327,7 @@ struct FrameParams {
   int32_t split_k;
   const float* face_boxcolor;  // RT_MODE_BOX_COLORS: [n_faces][4] summed box colours per face id
   // light sets beyond the 32 kernel-argument entries (rt_light_set): n_lights lights in device memory, in
-  // calculateColor's order, read by the memory-lights instantiations only (rt_kernels.h set_light); else null
+  // calculateColor's order, read by the memory-lights instantiations only (rt_shade.h set_light); else null
   const Light* light_set;
 };
 

@@ -89,7 +89,7 @@ static void world_bounds(const HostScene& hs, float lo[3], float hi[3]) {
   for (int k = 0; k < 3; k++) { lo[k] = w.lo[k]; hi[k] = w.hi[k]; }
 }
 
-// Reference-box certificates (TriRec64::box kBoxCertBit). The accept path's box fast path (rt_kernels.h
+// Reference-box certificates (TriRec64::box kBoxCertBit). The accept path's box fast path (rt_traverse.h
 // accept_candidate) accepts a candidate lane whose object-space hit point X = Minv p lies inside the
 // face's reference box by m_k = 1e-5 ((hi - lo) + |lo| + |hi| + |o2_k|) per axis, o2 the ray's
 // object-space origin -- margins far above the rounding of the reference's intersectBox

@@ -3,7 +3,7 @@
 // and correctly rounded divisions, everything compiled with -ffp-contract=off, so both give the same bits.
 //
 // The key orders rays so that 64 consecutive ones walk nearly the same root-to-leaf paths; it never decides a
-// result (rt_kernels.h k_rays). 32 bits:
+// result (rt_ray_kernels.h k_rays). 32 bits:
 //   bit 31     the ray is degenerate: a NaN or infinite component of its origin or direction, or a direction of
 //              all zeros. Such rays sort last, among themselves by index (the other bits are 0), and are
 //              traced as they are.

@@ -1,7 +1,7 @@
 // rt_rays.hip -- ray-list queries of the MI355X ray-traversal library: the device-resident, stream-ordered
 // path (rt_trace_stream, rt_rays_camera), its coherence reorder (key kernel + radix sort + indexed packets),
 // and the host-pointer entry points (rt_trace_closest and its siblings), which are "upload, stream path,
-// download". The packet kernels themselves are rt_kernels.h k_rays / k_rays_color / k_rays_depth; the stage kernels
+// download". The packet kernels themselves are rt_ray_kernels.h k_rays / k_rays_color / k_rays_depth; the stage kernels
 // of RT_RAYS_WAVEFRONT are rt_wavefront.h, their host glue (enqueue_wavefront) is here.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -10,7 +10,9 @@
 #include <vector>
 
 #include "rt_device.h"
+#include "rt_ray_kernels.h"
 #include "rt_raykey.h"
+#include "rt_variant_api.h"
 #include "rt_wavefront.h"
 
 namespace rt {

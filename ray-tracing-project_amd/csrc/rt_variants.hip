@@ -12,7 +12,10 @@
 //   1048576  two 8x8 packets per wave (dual-chain, k_primary_dual)
 //   4194304  PRIMARY descent by a conservative frustum (interval) test of the packet (k_primary_frustum)
 // Their measurements: DESIGN.md section 5 (the "Measured design decisions" table).
-#include "rt_kernels.h"
+#include "rt_frame_kernels.h"
+#include "rt_hip.h"
+#include "rt_ray_kernels.h"
+#include "rt_variant_api.h"
 
 namespace rt {
 

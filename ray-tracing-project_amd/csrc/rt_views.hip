@@ -1,6 +1,6 @@
 // rt_views.hip -- view batches of the MI355X ray-traversal library: rt_render_views / rt_render_views_lit render n
 // cameras of one scene, one frame shape and one set of lights in a single launch, straight into the caller's
-// device buffers on the caller's stream. The kernels are rt_kernels.h k_views_primary / k_views_depth (the frame
+// device buffers on the caller's stream. The kernels are rt_view_kernels.h k_views_primary / k_views_depth (the frame
 // kernels' arithmetic under a per-view camera record); which of them runs, and every refusal, is rt_dispatch.h
 // plan_views. The camera records live in a scene-owned device array (rt_scene::ViewScratch).
 // rt_render_views_ss / _ss_lit are the same batches with a sample pattern: S rays per pixel averaged in the launch
@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "rt_device.h"
+#include "rt_view_kernels.h"
 
 namespace rt {
 

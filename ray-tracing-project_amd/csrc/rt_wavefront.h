@@ -1,5 +1,5 @@
 // rt_wavefront.h -- the wavefront path of rt_trace_stream_color (RT_RAYS_WAVEFRONT): traceRay's level loop
-// (rt_kernels.h k_render_depth / trace_depth) cut into stage kernels, so that the rays of every stage can be regrouped into
+// (rt_trace_ray.h k_render_depth / trace_depth) cut into stage kernels, so that the rays of every stage can be regrouped into
 // packets of their own. Included only by rt_rays.hip, which holds the host glue (enqueue_wavefront).
 //
 // Level d = 0 .. D-1 of a call (D = max_depth, FULL = shadow rays and at least one light):
@@ -34,7 +34,7 @@
 // = 124 + 12 D bytes (172 B at D = 4, 316 B at D = 16), plus hipcub's temporary storage (a few bytes per ray) and,
 // with RT_RAYS_REORDER, the 16 B of level 0's sort (rt_rays.hip ScratchView).
 #pragma once
-#include "rt_kernels.h"
+#include "rt_trace_ray.h"
 #include "rt_raykey.h"
 
 namespace rt {

@@ -3,7 +3,7 @@
 The reference tests every box of its flat partition and culls nothing (src/flyscene.cpp:381-391), and its
 fly camera can move anywhere (dependencies/tucano/tucano/utils/flycamera.hpp:196-202). The GPU culls with
 a BVH whose boxes carry a static, scene-scale pad plus a per-ray pad proportional to the ray origin's
-magnitude (setup_cull, rt_kernels.h). These tests put the origin where the rounding
+magnitude (setup_cull, rt_traverse.h). These tests put the origin where the rounding
 of the reference's hit point P = o + t d is largest relative to the scene -- eyes at 50 and 500 scene
 extents (narrow fields of view, so the scene still fills the frame), eyes at 3-7 extents (inside the range
 where certified faces skip the reference box predicate), a grazing view along a face plane,

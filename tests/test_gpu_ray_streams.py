@@ -273,7 +273,7 @@ def test_reorder_lowers_the_wave_node_fetches(rt, scenes):
     """5. 64x48 cornell camera rays under a fixed shuffle: the reordered trace fetches strictly fewer node records
     per wave than the in-order one.
 
-    ST_NODE / ST_TRI (per-ray counts) are not compared: in the binary packet loop (rt_kernels.h traverse) a ray's
+    ST_NODE / ST_TRI (per-ray counts) are not compared: in the binary packet loop (rt_traverse.h traverse) a ray's
     box test is cut off at its current closest hit (tcut = h.t) and the near child is chosen by the wave's
     majority vote, so which nodes a ray still wants depends on the rays sharing its wave. Rays and hits do not."""
     W, H = 64, 48

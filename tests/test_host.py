@@ -113,7 +113,7 @@ def test_camera_path_matches_flycam(rt, dxyz):
 
 
 def test_moving_camera_prediction_geometry(rt):
-    """The moving camera's cost-map prediction (rt_kernels.h wave_clock_end, FrameParams::pred): a hit at distance t
+    """The moving camera's cost-map prediction (rt_frame_wave.h wave_clock_end, FrameParams::pred): a hit at distance t
     along pixel (px, py)'s view-space direction (a px + b, c py + e, -1), moved by the camera's last step
     (rt_frame.hip camera_step: the translation of V_n V_(n-1)^-1) and projected back, lands on the pixel where the
     same world point appears in the path's next frame. The same algebra as the kernel, in float64, against the

@@ -3,7 +3,7 @@
 
 The traversal loops issue scalar loads from inline asm whose completion the compiler does not track:
 prefetches into "sink" SGPRs, carried across loop iterations and retired by a later s_waitcnt (node
-loads, child prefetches: rt_kernels.h sload_node_pf_carry, traverse_wide_fast). Scalar loads return
+loads, child prefetches: rt_traverse.h sload_node_pf_carry, traverse_wide_fast). Scalar loads return
 out of order and write their destination whenever the data arrives, so between such a load and the next
 `s_waitcnt lgkmcnt(0)` no instruction may read its destination SGPRs (stale value), write them (the late
 load would overwrite the new value: the round-2 fault, profiles/ab/r02_pf_carry_ab.txt), or copy them.

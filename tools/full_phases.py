@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The FULL megakernel's packet walks by phase, from the counting run (RT_FRAME_STATS,
-rt_debug_counters slots ST_PW .. ST_PH, csrc/rt_kernels.h): per phase (primary, shadows of the primary hits,
+rt_debug_counters slots ST_PW .. ST_PH, csrc/rt_traverse.h): per phase (primary, shadows of the primary hits,
 reflection, shadows of the reflection hits) the wave-level walks, the mean active lanes at a walk's entry, node
 steps and triangle tests (per walk and as a share of the frame's), and the secondary phases' node steps by the
 walk's active lanes (1-8, 9-16, 17-32, 33-48, 49-64). One JSON line per workload.

@@ -1,6 +1,6 @@
 """Packet -> per-lane hybrid traversal model from the counting run (C3 and C2 frames).
 
-The counting traversal (rt_kernels.h traverse<STATS>) records, per wave:
+The counting traversal (rt_traverse.h traverse<STATS>) records, per wave:
   * how many lanes entered each node step / leaf visit (histogram: 0, 1, 2-3, 4-7, 8-15, 16-31, 32-64 lanes);
   * for thresholds k = 4, 8, 16: the node steps / triangle tests the packet spends in "switched regions"
     (subtrees entered by fewer than k lanes), and what walking those regions one ray per lane would cost

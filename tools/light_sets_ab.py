@@ -9,7 +9,7 @@ side -- after one discarded process, which meets the GPU's clocks ramping up out
       (bunny: at the default light's place; cornell: inside the box), the memory-lights kernel with the wave-level
       occluder cache (the default) against the same kernel without it (variant 16777216); plus, untimed, the wave
       node / triangle record fetches of a counting frame of each. --alt NAME=LIB (repeatable) adds a side that runs
-      the cached kernel of another build of the library, e.g. one compiled with another kOccK (rt_kernels.h);
+      the cached kernel of another build of the library, e.g. one compiled with another kOccK (rt_traverse.h);
       --scenes / --counts narrow the section
   (b) memory path against kernel arguments: 32 ring lights on the bunny through rt_render_lit, k_render_depth reading
       them from the kernel arguments (variant 65536), from memory without the cache (8388608 | 16777216) and from
