@@ -247,6 +247,52 @@ typedef struct rt_update_stats {
   double sah_cost;          /* rt_debug_tree_cost(k_trav 0.7) out[0] after the update */
 } rt_update_stats;
 int rt_scene_update(rt_scene* s, const rt_mesh_desc* mesh, rt_update_stats* stats /* may be NULL */);
+/* ---------------------------------------------------------------------------------------------
+ * Device-resident geometry updates (additive; feature test: RT_HAS_DEVICE_UPDATE; RT_API_VERSION stays 4)
+ *
+ * rt_scene_update_device(s, g, hip_stream, stats) is rt_scene_update for a caller whose geometry lives in device
+ * memory (a mesh deformed by kernels or torch every step): the three coordinate arrays are read where they are,
+ * and every stage of the update -- the per-vertex and per-face invariants, the reference-box partition with its
+ * ranks, the face flags, the static pad's bounds, the refit -- runs on the scene's device (devices[0]; replicas
+ * receive the changed regions by device copy, as for rt_scene_update). The topology is the scene's own (counts,
+ * face_vertex_ids, face_material_ids) and is not passed again. shape_model_matrix and materials are host
+ * pointers; NULL keeps the scene's.
+ *
+ * Contract: after RT_OK the scene is, bit for bit, the scene rt_scene_update produces from a host rt_mesh_desc
+ * holding the same three arrays, matrix and materials -- hence the scene rt_scene_create makes from them: every
+ * query of the rt_scene_update contract, and rt_scene_ref_boxes, rt_scene_ray_bounds, rt_debug_scene_flags,
+ * rt_debug_scene_records, rt_debug_validate_bvh, rt_debug_tree_cost, rt_scene_save, rt_debug_ray. The host half
+ * of the scene is refreshed from the device at its first host reader; nothing is computed twice.
+ *
+ * hip_stream is the stream on which the caller produced the arrays: the library reads them behind an event it
+ * records there (NULL: the default stream). The call is synchronous, with rt_scene_update's waits; on return the
+ * device data is the new geometry and the caller's arrays are no longer read.
+ *
+ * Refusals, each checked before anything is queued and leaving the scene exactly as it was: a NULL scene or
+ * geometry, a NULL array while its count is positive, a replica handle -> RT_ERR_INVALID; a wide_tree = 1 scene
+ * -> RT_ERR_UNSUPPORTED; a host-only scene -> RT_ERR_NO_DEVICE; an array that is host memory or another
+ * device's -> RT_ERR_INVALID. Any later failure has rt_scene_update's semantics: update again, successfully, or
+ * destroy the scene.
+ *
+ * Coordinates that are NaN, infinite or beyond 1e30 in magnitude (object or world space) are detected on the
+ * device; the call then downloads the three arrays and runs rt_scene_update on them (bounds_on_device = 0, the
+ * stats rt_scene_update's). A scene without faces takes the same route. These are the only host fallbacks.
+ *
+ * rt_update_stats for this call: prep_ms = device time of the invariant kernels; boxes_ms = the partition (its
+ * pass loop, on the device's timeline); records_ms = ranks, face flags and their small uploads; refit_ms = the
+ * refit kernels; upload_ms = what follows on the host side: the box image, materials, a host-built scene's
+ * quantised tree, the replicas' copies; total_ms = wall time after the waits.
+ * ------------------------------------------------------------------------------------------- */
+#define RT_HAS_DEVICE_UPDATE 1
+typedef struct rt_device_geometry {
+  const float* vertices;           /* device [n_vertices][4], object space (w as in rt_mesh_desc) */
+  const float* vertex_normals;     /* device [n_vertices][3] */
+  const float* face_normals;       /* device [n_faces][3]    */
+  const float* shape_model_matrix; /* host [16] column-major, NULL = keep the scene's */
+  const rt_material* materials;    /* host [n_materials of the scene], NULL = keep */
+} rt_device_geometry;
+int rt_scene_update_device(rt_scene* s, const rt_device_geometry* g, void* hip_stream,
+                           rt_update_stats* stats /* may be NULL */);
 /* The device-form image of the scene's records: which = 0 the binary nodes (64 B each), 1 the triangle records
  * in leaf order (64 B), 2 the per-slot shading records (48 B). Downloaded from the device for a device scene;
  * for a host-only scene built the way the upload builds it. *n_bytes = the image's size; out may be NULL

@@ -22,6 +22,7 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <vector>
 
 #include "rt_hip.h"
@@ -33,14 +34,7 @@ constexpr int kBS = 1024;      // threads per box
 constexpr int kWaves = kBS / 64;
 constexpr int kChunk = 2048;   // faces per staged chunk of the sequential sum (2 x 24 KB LDS)
 
-// one box of the partition (BoundingBox low / high / failed + its segment)
-struct DBox {
-  float low[3], high[3];
-  int32_t start, count;
-  int32_t failed[3];
-  int32_t result;  // splitBox outcome: 1 = split (child written), -1 = every axis failed
-};
-static_assert(sizeof(DBox) == 48, "DBox layout");
+// (one box of the partition, DBox: rt_scene.h)
 
 struct Pair {
   float v;
@@ -282,48 +276,24 @@ __global__ __launch_bounds__(kBS) void k_split_pass(DBox* boxes, DBox* child, fl
 
 }  // namespace
 
-int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes,
-                        double* gpu_ms, bool* nonfinite_out) {
-  const int nf = hs.nf;
+// The partition itself, on stream st: the faces' coordinates gathered from the device arrays v4 / fidx, the first box
+// fitted, then the passes of generateBoundingBoxes (flyscene.cpp:404-417), each one launch and one round trip of
+// the small box records. On return the stream is idle, `boxes` holds every box in creation order (its segment:
+// start, count) and w.d_ids the faces in segment order. *nonfinite: some coordinate is not finite, nothing built.
+int ref_box_passes(void* stream, const float* d_v4, const uint32_t* d_fidx, int nf, int32_t min_faces, int32_t max_boxes,
+                   BoxWork& w, std::vector<DBox>& boxes, bool* nonfinite_out) {
+  hipStream_t st = (hipStream_t)stream;
   *nonfinite_out = false;
-  HIPCHECK(hipSetDevice(device));
-  PhaseTimer pt("boxes-gpu");
-  hipStream_t st;
-  st = (hipStream_t)build_stream(device);
-  if (!st) return RT_ERR_HIP;
-  BuildScratch bs(st);
-  float *d_v4 = nullptr, *d_fv = nullptr, *d_fvt = nullptr;
-  uint32_t* d_fidx = nullptr;
-  int32_t *d_ids = nullptr, *d_idt = nullptr, *d_flag = nullptr;
-  DBox *d_boxes = nullptr, *d_child = nullptr;
-  HIPCHECK(bs.alloc(d_v4, 16 * (size_t)hs.nv));
-  HIPCHECK(bs.alloc(d_fidx, 12 * (size_t)nf));
-  HIPCHECK(bs.alloc(d_fv, 36 * (size_t)nf));
-  HIPCHECK(bs.alloc(d_fvt, 36 * (size_t)nf));
-  HIPCHECK(bs.alloc(d_ids, 4 * (size_t)nf));
-  HIPCHECK(bs.alloc(d_idt, 4 * (size_t)nf));
-  HIPCHECK(bs.alloc(d_flag, 4));
-  // todo / child records of one pass: at most every box splits, and a pass can hold all boxes
-  size_t cap = 1024;
-  HIPCHECK(bs.alloc(d_boxes, cap * sizeof(DBox)));
-  HIPCHECK(bs.alloc(d_child, cap * sizeof(DBox)));
-  HIPCHECK(bs.make_timer());
-  pt.mark("alloc");
-  // pageable sources through the pinned staging copies (h2d; a plain async copy from pageable memory runs
-  // at ~1 GB/s)
-  if (int rc = h2d(d_v4, v4, 16 * (size_t)hs.nv)) return rc;
-  if (int rc = h2d(d_fidx, hs.fidx.data(), 12 * (size_t)nf)) return rc;
-  pt.mark("h2d");
+  float *d_fv = w.d_fv, *d_fvt = w.d_fvt;
+  int32_t *d_ids = w.d_ids, *d_idt = w.d_idt, *d_flag = w.d_flag;
   HIPCHECK(hipMemsetAsync(d_flag, 0, 4, st));
-  HIPCHECK(bs.start());
-  hipLaunchKernelGGL(k_gather, dim3((nf + 255) / 256), dim3(256), 0, st, (const float*)d_v4, (const uint32_t*)d_fidx, nf,
-                     d_fv, d_ids, d_flag);
-  hipLaunchKernelGGL(k_fit_all, dim3(1), dim3(kBS), 0, st, (const float*)d_fv, nf, d_boxes);
+  hipLaunchKernelGGL(k_gather, dim3((nf + 255) / 256), dim3(256), 0, st, d_v4, d_fidx, nf, d_fv, d_ids, d_flag);
+  hipLaunchKernelGGL(k_fit_all, dim3(1), dim3(kBS), 0, st, (const float*)d_fv, nf, w.d_boxes);
   HIPCHECK(hipGetLastError());
   int32_t flag = 0;
-  std::vector<DBox> boxes(1);
+  boxes.assign(1, DBox{});
   HIPCHECK(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-  HIPCHECK(hipMemcpyAsync(boxes.data(), d_boxes, sizeof(DBox), hipMemcpyDeviceToHost, st));
+  HIPCHECK(hipMemcpyAsync(boxes.data(), w.d_boxes, sizeof(DBox), hipMemcpyDeviceToHost, st));
   HIPCHECK(hipStreamSynchronize(st));
   if (flag) { *nonfinite_out = true; return RT_OK; }
   // the passes of generateBoundingBoxes (flyscene.cpp:404-417)
@@ -346,14 +316,12 @@ int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_
     }
     if (todo.empty()) break;
     notDone = true;
-    if (todo.size() > cap) {
+    if (todo.size() > w.cap) {  // todo / child records of one pass: a pass can hold all boxes
+      size_t cap = w.cap;
       while (cap < todo.size()) cap *= 2;
-      DBox *nb = nullptr, *nc = nullptr;
-      HIPCHECK(bs.alloc(nb, cap * sizeof(DBox)));
-      HIPCHECK(bs.alloc(nc, cap * sizeof(DBox)));
-      d_boxes = nb;
-      d_child = nc;
+      if (const int rc = w.grow(w, cap)) return rc;
     }
+    DBox *d_boxes = w.d_boxes, *d_child = w.d_child;
     kids.resize(todo.size());
     HIPCHECK(hipMemcpyAsync(d_boxes, todo.data(), todo.size() * sizeof(DBox), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_split_pass, dim3((unsigned)todo.size()), dim3(kBS), 0, st, d_boxes, d_child, d_fv, d_ids, d_fvt,
@@ -375,6 +343,53 @@ int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_
     for (size_t i = 0; i < todo.size(); i++)
       if (todo[i].result == 1) boxes.push_back(kids[i]);
   }
+  return RT_OK;
+}
+
+// rt_scene_create's and rt_scene_update's partition: the description's vertices and the face indices uploaded, the
+// passes, the face order downloaded into hs.boxes
+int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes,
+                        double* gpu_ms, bool* nonfinite_out) {
+  const int nf = hs.nf;
+  *nonfinite_out = false;
+  HIPCHECK(hipSetDevice(device));
+  PhaseTimer pt("boxes-gpu");
+  hipStream_t st;
+  st = (hipStream_t)build_stream(device);
+  if (!st) return RT_ERR_HIP;
+  BuildScratch bs(st);
+  float* d_v4 = nullptr;
+  uint32_t* d_fidx = nullptr;
+  BoxWork w;
+  HIPCHECK(bs.alloc(d_v4, 16 * (size_t)hs.nv));
+  HIPCHECK(bs.alloc(d_fidx, 12 * (size_t)nf));
+  HIPCHECK(bs.alloc(w.d_fv, 36 * (size_t)nf));
+  HIPCHECK(bs.alloc(w.d_fvt, 36 * (size_t)nf));
+  HIPCHECK(bs.alloc(w.d_ids, 4 * (size_t)nf));
+  HIPCHECK(bs.alloc(w.d_idt, 4 * (size_t)nf));
+  HIPCHECK(bs.alloc(w.d_flag, 4));
+  w.cap = 1024;
+  HIPCHECK(bs.alloc(w.d_boxes, w.cap * sizeof(DBox)));
+  HIPCHECK(bs.alloc(w.d_child, w.cap * sizeof(DBox)));
+  w.grow = [&bs](BoxWork& bw, size_t cap) -> int {  // (the old pair is released with the scratch)
+    DBox *nb = nullptr, *nc = nullptr;
+    HIPCHECK(bs.alloc(nb, cap * sizeof(DBox)));
+    HIPCHECK(bs.alloc(nc, cap * sizeof(DBox)));
+    bw.d_boxes = nb, bw.d_child = nc, bw.cap = cap;
+    return RT_OK;
+  };
+  HIPCHECK(bs.make_timer());
+  pt.mark("alloc");
+  // pageable sources through the pinned staging copies (h2d; a plain async copy from pageable memory runs
+  // at ~1 GB/s)
+  if (int rc = h2d(d_v4, v4, 16 * (size_t)hs.nv)) return rc;
+  if (int rc = h2d(d_fidx, hs.fidx.data(), 12 * (size_t)nf)) return rc;
+  pt.mark("h2d");
+  HIPCHECK(bs.start());
+  std::vector<DBox> boxes;
+  if (const int rc = ref_box_passes(st, d_v4, d_fidx, nf, min_faces, max_boxes, w, boxes, nonfinite_out)) return rc;
+  if (*nonfinite_out) return RT_OK;
+  int32_t* d_ids = w.d_ids;
   HIPCHECK(bs.stop());
   pt.mark("passes");
   std::vector<int32_t> ids(nf);

@@ -88,7 +88,7 @@ struct Reader {
 
 extern "C" int rt_scene_save(const rt_scene* s, const char* path) {
   if (!s || !path) { rt::set_error("rt_scene_save: null argument"); return RT_ERR_INVALID; }
-  if (const int rc = rt::host_mirror(s)) return rc;  // (hs.nodes / hs.tris after a device refit)
+  if (const int rc = rt::host_mirror_all(s)) return rc;  // (the host half after a device refit / device update)
   const rt::HostScene& hs = s->hs;
   std::unique_ptr<FILE, int (*)(FILE*)> fp(fopen(path, "wb"), fclose);
   if (!fp) { rt::set_error("rt_scene_save: cannot open %s", path); return RT_ERR_IO; }

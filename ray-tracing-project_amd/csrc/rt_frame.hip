@@ -183,6 +183,9 @@ static int ensure_face_boxcolor(rt_scene* s) {
     const int rc = rt_scene_set_box_colors(s, nullptr);
     if (rc) return rc;
   }
+  // (hs.ov3 after a device update: a replica's scene has mirrored before its workers run, rt_multi.hip)
+  if (!s->is_replica)
+    if (const int rc = host_mirror_geometry(s)) return rc;
   if (hs.ov3.size() != 3 * (size_t)hs.nv) { set_error("scene has no object-space vertices"); return RT_ERR_INVALID; }
   if (const int rc = drain_slots(s)) return rc;
   const size_t nf = (size_t)hs.nf, nb = hs.boxes.size();

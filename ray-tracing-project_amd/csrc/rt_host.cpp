@@ -299,6 +299,7 @@ extern "C" int rt_scene_set_box_colors(rt_scene* s, const float* colors3) {
 
 extern "C" int rt_scene_ref_boxes(const rt_scene* s, float* bounds6, int32_t* counts, int32_t* face_order) {
   if (!s) { rt::set_error("rt_scene_ref_boxes: null scene"); return RT_ERR_INVALID; }
+  if (const int rc = rt::host_mirror_geometry(s)) return rc;  // (the boxes' face lists after a device update)
   size_t off = 0;
   for (size_t i = 0; i < s->hs.boxes.size(); i++) {
     const rt::RefBox& b = s->hs.boxes[i];
@@ -432,6 +433,8 @@ extern "C" int rt_sample_pattern_jittered(int32_t nx, int32_t ny, rt_rand_state*
 #include "rt_raykey.h"
 
 const float* rt::scene_ray_bounds(rt_scene* s) {
+  // hs.wv after a device update: mirrored by the callers that can report a failure (rt_scene_ray_bounds, the ray
+  // lists' ensure_scratch); a replica is never asked -- lists and bounds go through its scene, whose HostScene it shares
   if (!s->ray_bounds_valid) {
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
     for (const rt::f3& v : s->hs.wv) {
@@ -453,6 +456,7 @@ const float* rt::scene_ray_bounds(rt_scene* s) {
 
 extern "C" int rt_scene_ray_bounds(rt_scene* s, float bounds6[6]) {
   if (!s || !bounds6) { rt::set_error("rt_scene_ray_bounds: null argument"); return RT_ERR_INVALID; }
+  if (const int rc = rt::host_mirror_geometry(s)) return rc;  // (hs.wv after a device update)
   memcpy(bounds6, rt::scene_ray_bounds(s), 24);
   return RT_OK;
 }

@@ -15,6 +15,8 @@
 
 #include "rt_host.h"
 
+#include "rt_faceflags.h"
+
 namespace rt {
 
 // A face whose interpolated normal (interpolateNormal, flyscene.cpp:594-599) can never be the zero
@@ -24,20 +26,8 @@ namespace rt {
 // far above rounding, so norm() != 0 and the reference never rejects the face for it; when A would
 // overflow the blend, the result is NaN, which the reference also accepts (NaN != 0).
 static bool safe_normal(const HostScene& hs, uint32_t f) {
-  const f3& w0 = hs.wv[hs.fidx[3 * f]];
-  const f3& w1 = hs.wv[hs.fidx[3 * f + 1]];
-  const f3& w2 = hs.wv[hs.fidx[3 * f + 2]];
-  const f3 e0 = sub(w1, w0), e2 = sub(w0, w2);
-  const float A = norm(cross(e0, neg(e2))) / 2;
-  if (!(A > 1e-30f) || !std::isfinite(A)) return false;
-  const f3& n = hs.fnn[f];
-  for (int k = 0; k < 3; k++) {
-    const f3& nk = hs.vnn[hs.fidx[3 * f + k]];
-    if (!std::isfinite(nk.x) || !std::isfinite(nk.y) || !std::isfinite(nk.z)) return false;
-    if (std::fabs(sqnorm(nk) - 1.0f) > 1e-3f) return false;
-    if (!(dot(n, nk) >= 0.5f)) return false;
-  }
-  return true;
+  const uint32_t* v = &hs.fidx[3 * (size_t)f];
+  return safe_normal_of(hs.wv[v[0]], hs.wv[v[1]], hs.wv[v[2]], hs.fnn[f], hs.vnn[v[0]], hs.vnn[v[1]], hs.vnn[v[2]]);
 }
 
 // conservative padding of every BVH child box: covers the reference's rounding of P = o + t d and of
@@ -116,7 +106,7 @@ float cert_origin_max(const HostScene& hs) {
 // model matrix whose linear part is not a uniform scale times a rotation certifies nothing
 // (model_is_similarity), and a face certifies only if its normal is within kCertNormalSin of the world
 // triangle's normal, with that projection offset (2 diam sin) added to the margin.
-constexpr double kCertNormalSin = 1e-3;
+// (kCertNormalSin: rt_faceflags.h)
 bool model_is_similarity(const float* M) {
   double c[3][3], n2[3];
   for (int j = 0; j < 3; j++) {
@@ -136,22 +126,8 @@ bool model_is_similarity(const float* M) {
 // sin of the angle between the face normal the edge tests use and the world triangle's normal (2 on
 // degenerate or non-finite input: never certified)
 static double face_normal_tilt(const HostScene& hs, uint32_t f) {
-  double w[3][3];
-  for (int j = 0; j < 3; j++) {
-    const f3& p = hs.wv[hs.fidx[3 * f + j]];
-    w[j][0] = p.x; w[j][1] = p.y; w[j][2] = p.z;
-  }
-  const double a[3] = {w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2]};
-  const double c[3] = {w[2][0] - w[0][0], w[2][1] - w[0][1], w[2][2] - w[0][2]};
-  const double g[3] = {a[1] * c[2] - a[2] * c[1], a[2] * c[0] - a[0] * c[2], a[0] * c[1] - a[1] * c[0]};
-  const f3& nf = hs.fnn[f];
-  const double n[3] = {nf.x, nf.y, nf.z};
-  const double gg = g[0] * g[0] + g[1] * g[1] + g[2] * g[2], nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-  if (!std::isfinite(gg) || !std::isfinite(nn) || !(gg > 0.0) || !(nn > 0.0)) return 2.0;
-  const double x[3] = {g[1] * n[2] - g[2] * n[1], g[2] * n[0] - g[0] * n[2], g[0] * n[1] - g[1] * n[0]};
-  const double dn = g[0] * n[0] + g[1] * n[1] + g[2] * n[2];
-  if (!(dn > 0.0)) return 2.0;  // opposite orientation: the edge tests' inside is the other side
-  return std::sqrt((x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) / (gg * nn));
+  const uint32_t* v = &hs.fidx[3 * (size_t)f];
+  return face_tilt_of(hs.wv[v[0]], hs.wv[v[1]], hs.wv[v[2]], hs.fnn[f]);
 }
 
 // The edge tests (flyscene.cpp:580-590) accept P when n.(e_k x (P - w_k)) >= 0 for the three world edges,
@@ -162,7 +138,7 @@ static double face_normal_tilt(const HostScene& hs, uint32_t f) {
 // its diameter, well inside the static pad's rounding allowance) is bounded by that projection; an
 // untilted scene keeps hs.av empty and its builds unchanged. (A normal facing away from the triangle
 // accepts nothing beyond rounding; its projection still bounds that.)
-constexpr double kBoundTilt = 1e-6;
+// (kBoundTilt: rt_faceflags.h)
 void accept_region(HostScene& hs) {
   hs.av.clear();
   std::atomic<bool> any{false};
@@ -174,17 +150,9 @@ void accept_region(HostScene& hs) {
   hs.av.resize(3 * (size_t)hs.nf);
   parallel_chunks((size_t)hs.nf, [&](size_t b, size_t e, int) {
     for (size_t f = b; f < e; f++) {
-      const f3& nf = hs.fnn[f];
-      const double n[3] = {nf.x, nf.y, nf.z}, nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
       const bool tilted = !(face_normal_tilt(hs, (uint32_t)f) <= kBoundTilt);
-      for (int j = 0; j < 3; j++) {
-        const f3& w = hs.wv[hs.fidx[3 * f + j]];
-        f3& p = hs.av[3 * f + j];
-        p = w;
-        if (!tilted || !(nn > 0.0) || !std::isfinite(nn)) continue;
-        const double s = (n[0] * w.x + n[1] * w.y + n[2] * w.z - (double)hs.fdist[f]) / nn;
-        p = f3{(float)(w.x - s * n[0]), (float)(w.y - s * n[1]), (float)(w.z - s * n[2])};
-      }
+      for (int j = 0; j < 3; j++)
+        hs.av[3 * f + j] = accept_vertex_of(hs.wv[hs.fidx[3 * f + j]], hs.fnn[f], hs.fdist[f], tilted);
     }
   });
 }
@@ -194,37 +162,8 @@ static bool box_certified(const HostScene& hs, uint32_t f, float Ro) {
   const double tilt = face_normal_tilt(hs, f);
   if (!(tilt <= kCertNormalSin)) return false;
   const RefBox& b = hs.boxes[hs.face_box[f]];
-  double v[3][3];
-  for (int j = 0; j < 3; j++)
-    for (int k = 0; k < 3; k++) {
-      v[j][k] = hs.ov3[3 * (size_t)hs.fidx[3 * f + j] + k];
-      if (!std::isfinite(v[j][k])) return false;
-    }
-  // edge lengths and the smallest angle (law of cosines, in double)
-  double L[3];
-  for (int j = 0; j < 3; j++) {
-    const double* a = v[j];
-    const double* c = v[(j + 1) % 3];
-    L[j] = std::sqrt((c[0] - a[0]) * (c[0] - a[0]) + (c[1] - a[1]) * (c[1] - a[1]) + (c[2] - a[2]) * (c[2] - a[2]));
-  }
-  const double diam = std::max(L[0], std::max(L[1], L[2]));
-  if (!(diam > 0.0)) return false;
-  for (int j = 0; j < 3; j++) {  // angle opposite edge j: between edges j+1 and j+2
-    const double a = L[(j + 1) % 3], c = L[(j + 2) % 3], o = L[j];
-    if (!(a > 0.0 && c > 0.0)) return false;
-    const double cosv = std::min(1.0, std::max(-1.0, (a * a + c * c - o * o) / (2.0 * a * c)));
-    const double s_half = std::sqrt(std::max(0.0, (1.0 - cosv) / 2.0));  // sin(theta / 2)
-    if (!(s_half >= 0.01)) return false;
-  }
-  for (int k = 0; k < 3; k++) {
-    const double lo = b.low[k], hi = b.high[k];
-    if (!std::isfinite(lo) || !std::isfinite(hi)) return false;
-    const double S = (hi - lo) + std::fabs(lo) + std::fabs(hi);
-    const double need = 1e-5 * (S + Ro) + 1e-30 + 1e-5 * S + 4e-4 * diam + 2.0 * tilt * diam;
-    for (int j = 0; j < 3; j++)
-      if (!(v[j][k] - lo >= need && hi - v[j][k] >= need)) return false;
-  }
-  return true;
+  const uint32_t* v = &hs.fidx[3 * (size_t)f];
+  return box_certified_of(&hs.ov3[3 * (size_t)v[0]], &hs.ov3[3 * (size_t)v[1]], &hs.ov3[3 * (size_t)v[2]], b.low, b.high, Ro, tilt);
 }
 
 // the flag bits of face f's triangle records (kSafeNormalBit, kBoxCertBit): derived from the geometry

@@ -115,6 +115,8 @@ static int render_multi(rt_scene* s, const rt_camera* cam, const rt_light* light
   };
   // the reference's default box colours (setRandomColor draws) reach every replica here, on the caller's
   // thread, before any worker reads its replica's colours
+  if (fr->mode == RT_MODE_BOX_COLORS)  // (the object-space vertices every replica's colour pass reads)
+    if (const int rc = host_mirror_geometry(s)) return rc;
   if (fr->mode == RT_MODE_BOX_COLORS && s->box_colors.size() != 3 * s->hs.boxes.size()) {
     const int rc = rt_scene_set_box_colors(s, nullptr);
     if (rc) return rc;

@@ -109,6 +109,7 @@ int ensure_scratch(rt_scene* s, size_t n, size_t tmp_bytes) {
       return RT_ERR_NOMEM;
     }
     r.capacity = cap;
+    if (const int rc = host_mirror_geometry(s)) return rc;  // (hs.wv after a device update)
     HIPCHECK(hipMemcpy(scratch_view(r).bounds, scene_ray_bounds(s), 24, hipMemcpyHostToDevice));
   }
   if (tmp_bytes > r.tmp_bytes) {

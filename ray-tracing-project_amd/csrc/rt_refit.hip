@@ -125,7 +125,7 @@ static int keep_on_device(T*& dst, const void* src, size_t bytes, int64_t& total
 }
 
 // the first update's one-time uploads and allocations
-static int refit_prepare(rt_scene* s) {
+int refit_prepare(rt_scene* s) {
   rt_scene::Refit& R = s->refit;
   if (R.device_ready) return RT_OK;
   const HostScene& hs = s->hs;
@@ -152,9 +152,46 @@ void refit_release(rt_scene* s) {
                   R.d_vnn, R.d_av, R.d_slotbox, R.d_face, R.d_fmat};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  // ... and what the device update's pipeline keeps (rt_update_device.hip)
+  void* more[] = {R.d_ov3, R.d_red, R.work.d_fv, R.work.d_fvt, R.work.d_ids, R.work.d_idt, R.work.d_flag, R.work.d_boxes,
+                  R.work.d_child, R.d_seg_start, R.d_seg_box, R.d_seg_first, R.d_box_bounds};
+  for (void* b : more)
+    if (b) (void)hipFree(b);
+  if (R.ev_in) (void)hipEventDestroy((hipEvent_t)R.ev_in);
+  for (void* e : R.ev_t)
+    if (e) (void)hipEventDestroy((hipEvent_t)e);
   RefitTopo keep = std::move(R.topo);
   R = rt_scene::Refit{};
   R.topo = std::move(keep);
+}
+
+// the three refit kernels on the scene's stream, over the per-vertex / per-face arrays on the device
+int refit_launch(rt_scene* s, float pad, bool av) {
+  rt_scene::Refit& R = s->refit;
+  const HostScene& hs = s->hs;
+  const RefitTopo& t = R.topo;
+  const uint32_t nn = (uint32_t)hs.nodes.size(), nt = (uint32_t)hs.tris.size(), nf = (uint32_t)hs.nf;
+  hipStream_t st = (hipStream_t)s->stream;
+  auto blocks = [](uint32_t n) { return dim3((n + 255u) / 256u); };
+  if (nt) {
+    hipLaunchKernelGGL(k_refit_slots, blocks(nt), dim3(256), 0, st, nt, nf, s->d_tris, reinterpret_cast<float4*>(s->d_fshade),
+                       R.d_slotbox, R.d_fidx, R.d_wv, R.d_vnn, R.d_face, R.d_fmat, av ? R.d_av : nullptr);
+    HIPCHECK(hipGetLastError());
+  }
+  const uint32_t nl = (uint32_t)t.leaf_handle.size();
+  if (nl) {
+    hipLaunchKernelGGL(k_refit_leaves, blocks(nl), dim3(256), 0, st, nl, nt, nn, R.d_leaf_handle, R.d_leaf_where, R.d_slotbox,
+                       s->d_nodes, pad);
+    HIPCHECK(hipGetLastError());
+  }
+  for (size_t L = t.level_off.size() - 1; L-- > 0;) {
+    const uint32_t n = t.level_off[L + 1] - t.level_off[L];
+    if (!n) continue;
+    hipLaunchKernelGGL(k_refit_level, blocks(n), dim3(256), 0, st, n, nn, R.d_level_nodes + t.level_off[L], R.d_node_where,
+                       s->d_nodes);
+    HIPCHECK(hipGetLastError());
+  }
+  return RT_OK;
 }
 
 int device_refit(rt_scene* s, const std::vector<TriRec64>& recs, float pad, double* upload_ms, double* refit_ms) {
@@ -191,25 +228,7 @@ int device_refit(rt_scene* s, const std::vector<TriRec64>& recs, float pad, doub
   HIPCHECK(hipEventCreate(&e0));
   HIPCHECK(hipEventCreate(&e1));
   HIPCHECK(hipEventRecord(e0, st));
-  auto blocks = [](uint32_t n) { return dim3((n + 255u) / 256u); };
-  if (nt) {
-    hipLaunchKernelGGL(k_refit_slots, blocks(nt), dim3(256), 0, st, nt, nf, s->d_tris, reinterpret_cast<float4*>(s->d_fshade),
-                       R.d_slotbox, R.d_fidx, R.d_wv, R.d_vnn, R.d_face, R.d_fmat, hs.av.empty() ? nullptr : R.d_av);
-    HIPCHECK(hipGetLastError());
-  }
-  const uint32_t nl = (uint32_t)t.leaf_handle.size();
-  if (nl) {
-    hipLaunchKernelGGL(k_refit_leaves, blocks(nl), dim3(256), 0, st, nl, nt, nn, R.d_leaf_handle, R.d_leaf_where, R.d_slotbox,
-                       s->d_nodes, pad);
-    HIPCHECK(hipGetLastError());
-  }
-  for (size_t L = t.level_off.size() - 1; L-- > 0;) {
-    const uint32_t n = t.level_off[L + 1] - t.level_off[L];
-    if (!n) continue;
-    hipLaunchKernelGGL(k_refit_level, blocks(n), dim3(256), 0, st, n, nn, R.d_level_nodes + t.level_off[L], R.d_node_where,
-                       s->d_nodes);
-    HIPCHECK(hipGetLastError());
-  }
+  if ((rc = refit_launch(s, pad, !hs.av.empty()))) return rc;
   HIPCHECK(hipEventRecord(e1, st));
   HIPCHECK(hipStreamSynchronize(st));
   float ms = 0.0f;
@@ -316,6 +335,55 @@ int host_mirror(const rt_scene* cs) {
   }
   if (nt && (rc = d2h(hs.tris.data(), s->d_tris, nt * 64))) return rc;
   s->host_stale = false;
+  return RT_OK;
+}
+
+// hs's per-vertex / per-face arrays from what rt_scene_update_device keeps on the device: nothing is recomputed
+int host_mirror_geometry(const rt_scene* cs) {
+  if (!cs->geom_stale) return RT_OK;
+  rt_scene* s = const_cast<rt_scene*>(cs);
+  HIPCHECK(hipSetDevice(s->device));
+  HostScene& hs = s->hs;
+  rt_scene::Refit& R = s->refit;
+  const size_t nv = (size_t)hs.nv, nf = (size_t)hs.nf;
+  int rc;
+  hs.ov3.resize(3 * nv);
+  hs.wv.resize(nv);
+  hs.vnn.resize(nv);
+  if (nv) {
+    if ((rc = d2h(hs.ov3.data(), R.d_ov3, 12 * nv))) return rc;
+    if ((rc = d2h(hs.wv.data(), R.d_wv, 12 * nv))) return rc;
+    if ((rc = d2h(hs.vnn.data(), R.d_vnn, 12 * nv))) return rc;
+  }
+  hs.fnn.resize(nf);
+  hs.fdist.resize(nf);
+  hs.face_rank.assign(nf, 0);
+  hs.face_box.assign(nf, 0);
+  hs.av.clear();
+  if (nf) {
+    std::unique_ptr<FaceWords[]> fw(new FaceWords[nf]);
+    if ((rc = d2h(fw.get(), R.d_face, sizeof(FaceWords) * nf))) return rc;
+    parallel_for(nf, [&](size_t b, size_t e) {
+      for (size_t f = b; f < e; f++) {
+        hs.fnn[f] = f3{fw[f].nx, fw[f].ny, fw[f].nz};
+        hs.fdist[f] = fw[f].dist;
+        hs.face_rank[f] = fw[f].rank;
+        hs.face_box[f] = fw[f].box & kBoxIndexMask;
+      }
+    });
+    if (R.tilted) {
+      hs.av.resize(3 * nf);
+      if ((rc = d2h(hs.av.data(), R.d_av, 36 * nf))) return rc;
+    }
+    std::vector<int32_t> ids(nf);
+    if ((rc = d2h(ids.data(), R.work.d_ids, 4 * nf))) return rc;
+    for (size_t i = 0; i < hs.boxes.size() && i < R.boxes.size(); i++) {
+      const DBox& d = R.boxes[i];
+      if (d.start < 0 || d.count < 0 || (size_t)d.start + (size_t)d.count > nf) { set_error("host mirror: bad box segment"); return RT_ERR_HIP; }
+      hs.boxes[i].faces.assign(ids.begin() + d.start, ids.begin() + d.start + d.count);
+    }
+  }
+  s->geom_stale = false;
   return RT_OK;
 }
 

@@ -71,6 +71,26 @@ struct HostScene {
 // vertex coordinate is not finite and nothing was built (the caller uses the host builder)
 int gpu_build_ref_boxes(int device, HostScene& hs, const float* v4, int32_t min_faces, int32_t max_boxes,
                         double* gpu_ms, bool* nonfinite);
+// One box of the device partition (BoundingBox low / high / failed + its segment of the permuted face arrays), the
+// partition's working buffers, and the partition over device arrays (rt_boxes.hip ref_box_passes, which
+// gpu_build_ref_boxes wraps and the device update calls with a caller's vertices): grow(w, cap) replaces
+// d_boxes / d_child by arrays of cap records.
+struct DBox {
+  float low[3], high[3];
+  int32_t start, count;
+  int32_t failed[3];
+  int32_t result;  // splitBox outcome: 1 = split (child written), -1 = every axis failed
+};
+static_assert(sizeof(DBox) == 48, "DBox layout");
+struct BoxWork {
+  float *d_fv = nullptr, *d_fvt = nullptr;                             // [nf][9] coordinates, and their scratch
+  int32_t *d_ids = nullptr, *d_idt = nullptr, *d_flag = nullptr;      // [nf] face ids, their scratch, one flag word
+  DBox *d_boxes = nullptr, *d_child = nullptr;                         // [cap] records of one pass
+  size_t cap = 0;
+  std::function<int(BoxWork&, size_t)> grow;
+};
+int ref_box_passes(void* stream, const float* d_v4, const uint32_t* d_fidx, int nf, int32_t min_faces, int32_t max_boxes,
+                   BoxWork& w, std::vector<DBox>& boxes, bool* nonfinite);
 int gpu_build_ploc(int device, const std::vector<TriRec64>& face_recs, const float lo[3], const float hi[3],
                    int leaf_size, int radius, float k_trav, std::vector<int32_t>& child2, std::vector<float>& box6,
                    std::vector<uint8_t>& leaf, double* gpu_ms, int* iterations, int rule);
@@ -329,10 +349,33 @@ struct rt_scene {
     float *d_wv = nullptr, *d_vnn = nullptr, *d_av = nullptr, *d_slotbox = nullptr;
     rt::FaceWords* d_face = nullptr;
     int32_t* d_fmat = nullptr;
+    // rt_scene_update_device (rt_update_device.hip): what its pipeline keeps beside the arrays above -- the raw
+    // object-space xyz, the reduction words, the partition's working buffers (work.d_ids: the face order), the
+    // boxes' segments and bounds on the device, its events -- allocated at the first device update, and the
+    // boxes' segments of the latest one (what the host mirror cuts the face order by)
+    bool update_ready = false, fmat_sent = false;
+    float* d_ov3 = nullptr;
+    uint32_t* d_red = nullptr;
+    rt::BoxWork work;
+    int32_t* d_seg_start = nullptr;
+    uint32_t *d_seg_box = nullptr, *d_seg_first = nullptr;
+    float* d_box_bounds = nullptr;
+    size_t seg_cap = 0;
+    void* ev_in = nullptr;
+    void* ev_t[5] = {};
+    std::vector<rt::DBox> boxes;
+    std::vector<uint32_t> h_first, h_seg_box, h_seg_first;  // host staging of the segments and bounds of one update
+    std::vector<int32_t> h_seg_start;
+    std::vector<float> h_box_bounds;
+    bool tilted = false;  // some face of the latest device update is bounded by its accept-region triangle (d_av)
   } refit;
   // After a device refit the device holds the node boxes and the slot records; hs.nodes / hs.tris are refreshed
   // from it by the first host reader (host_mirror)
   bool host_stale = false;
+  // After rt_scene_update_device the per-vertex / per-face arrays of hs (ov3, wv, vnn, fnn, fdist, av, every box's
+  // face list, face_rank / face_box) are stale as well: refreshed from the arrays the pipeline keeps on the device
+  // by the first host reader (host_mirror_geometry); a host rt_scene_update overwrites them all
+  bool geom_stale = false;
 };
 
 namespace rt {
@@ -368,4 +411,20 @@ int device_reupload(rt_scene* s);
 int device_update_rest(rt_scene* s, bool replace4, bool boxes_changed);
 int host_mirror(const rt_scene* s);
 void refit_release(rt_scene* s);
+// ---- rt_scene_update_device ----
+// rt_refit.hip: refit_prepare's one-time uploads; the three refit kernels queued on the scene's stream over the
+// device arrays (av: with the accept-region triangles); hs's per-vertex / per-face arrays refreshed from the device
+// when stale, and both mirrors at once (every host reader of the geometry)
+int refit_prepare(rt_scene* s);
+int refit_launch(rt_scene* s, float pad, bool av);
+int host_mirror_geometry(const rt_scene* s);
+inline int host_mirror_all(const rt_scene* s) {
+  if (const int rc = host_mirror(s)) return rc;
+  return host_mirror_geometry(s);
+}
+// rt_update.cpp: what both update paths end with (the quantised tree of a host-built scene, the invalidations, the
+// reference boxes / materials / replicas on the device), and the two scalars from their reduced inputs
+int update_finish(rt_scene* s, size_t boxes_before);
+float static_pad_of_bounds(const float lo[3], const float hi[3]);
+float cert_origin_of(const float* M, float max_abs_coordinate);
 }  // namespace rt

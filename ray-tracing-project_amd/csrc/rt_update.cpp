@@ -84,6 +84,32 @@ static bool refit_on_device(const HostScene& hs) {
   return ok;
 }
 
+// the quantised 4-wide tree of a host-built scene from the refit binary tree (create's depth rule), the
+// invalidations, and the device's reference boxes, materials and replicas
+int update_finish(rt_scene* s, size_t boxes_before) {
+  HostScene& hs = s->hs;
+  int rc;
+  const bool replace4 = s->builder_used == RT_BUILDER_SAH || s->builder_used == RT_BUILDER_SBVH;
+  if (replace4) {
+    if ((rc = host_mirror(s))) return rc;
+    build_bvh4(hs);
+    if (3 * hs.depth4 + 4 > kStack4) hs.nodes4.clear();
+  }
+  const bool boxes_changed = hs.boxes.size() != boxes_before;
+  if (boxes_changed) s->box_colors.clear();  // "not set yet"
+  s->face_boxcolor_valid = false;
+  s->ray_bounds_valid = false;
+  s->lpt.valid = false;
+  if (s->device != RT_DEVICE_NONE && (rc = device_update_rest(s, replace4, boxes_changed))) return rc;
+  return RT_OK;
+}
+
+float static_pad_of_bounds(const float lo[3], const float hi[3]) { return bvh_pad(lo, hi); }
+float cert_origin_of(const float* M, float R) {  // (cert_origin_max over the reduced maximum)
+  if (!model_is_similarity(M)) return 0.0f;
+  return std::isfinite(R) ? 16.0f * R : 0.0f;
+}
+
 }  // namespace rt
 
 extern "C" int rt_scene_update(rt_scene* s, const rt_mesh_desc* d, rt_update_stats* stats) {
@@ -157,23 +183,9 @@ extern "C" int rt_scene_update(rt_scene* s, const rt_mesh_desc* d, rt_update_sta
     }
   }
   pt.mark("refit");
-  // the quantised 4-wide tree of a host-built scene, from the refit binary tree, with create's depth rule
-  const bool replace4 = s->builder_used == RT_BUILDER_SAH || s->builder_used == RT_BUILDER_SBVH;
-  if (replace4) {
-    if ((rc = rt::host_mirror(s))) return rc;
-    rt::build_bvh4(hs);
-    if (3 * hs.depth4 + 4 > rt::kStack4) hs.nodes4.clear();
-  }
-  pt.mark("bvh4");
-  const bool boxes_changed = hs.boxes.size() != boxes_before;
-  if (boxes_changed) s->box_colors.clear();  // "not set yet"
-  s->face_boxcolor_valid = false;
-  s->ray_bounds_valid = false;
-  s->lpt.valid = false;
-  if (on_device) {
-    if ((rc = rt::device_update_rest(s, replace4, boxes_changed))) return rc;
-    st.upload_ms += lap();
-  }
+  s->geom_stale = false;  // (every array a device update leaves stale has been written above)
+  if ((rc = rt::update_finish(s, boxes_before))) return rc;
+  if (on_device) st.upload_ms += lap();
   st.total_ms = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
   if (stats) {
     double cost[4];

@@ -153,7 +153,7 @@ struct Validator {
 
 extern "C" int rt_debug_scene_flags(const rt_scene* s, int64_t counts[3], float* cert_origin_max, uint32_t* face_flags) {
   if (!s || !counts) { rt::set_error("rt_debug_scene_flags: null argument"); return RT_ERR_INVALID; }
-  if (const int rc = rt::host_mirror(s)) return rc;  // (hs.nodes / hs.tris after a device refit)
+  if (const int rc = rt::host_mirror_all(s)) return rc;  // (hs.nodes / hs.tris after a device refit, ov3 after a device update)
   counts[0] = (int64_t)s->hs.tris.size();
   counts[1] = counts[2] = 0;
   if (face_flags) memset(face_flags, 0, sizeof(uint32_t) * (size_t)s->hs.nf);
@@ -214,7 +214,7 @@ extern "C" int rt_debug_tree_cost(const rt_scene* s, double k_trav, double out[4
 
 extern "C" int rt_debug_validate_bvh(const rt_scene* s, int64_t info[7]) {
   if (!s || !info) { rt::set_error("rt_debug_validate_bvh: null argument"); return RT_ERR_INVALID; }
-  if (const int rc = rt::host_mirror(s)) return rc;  // (hs.nodes / hs.tris after a device refit)
+  if (const int rc = rt::host_mirror_all(s)) return rc;  // (hs.nodes / hs.tris after a device refit, the bound vertices after a device update)
   const rt::HostScene& hs = s->hs;
   Validator v{hs, std::vector<int>(hs.tris.size()), std::vector<int>(hs.tris.size())};
   v.strict = hs.tris.size() == (size_t)hs.nf;

@@ -49,7 +49,7 @@ EXPORTS = [
     "rt_render_views", "rt_render_views_lit", "rt_debug_view_plan",
     "rt_sample_pattern_grid", "rt_sample_pattern_jittered", "rt_render_views_ss", "rt_render_views_ss_lit",
     "rt_render_ss", "rt_debug_sample_plan",
-    "rt_scene_update", "rt_debug_scene_records",
+    "rt_scene_update", "rt_debug_scene_records", "rt_scene_update_device",
 ]
 RT_MAX_VIEWS = 65536
 RT_MAX_SAMPLES = 64
@@ -137,6 +137,11 @@ class UpdateStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class DeviceGeometry(C.Structure):
+    _fields_ = [("vertices", C.c_void_p), ("vertex_normals", C.c_void_p), ("face_normals", C.c_void_p),
+                ("shape_model_matrix", C.c_void_p), ("materials", C.c_void_p)]
 
 
 class Frame(C.Structure):
@@ -271,6 +276,9 @@ def lib():
         if hasattr(L, "rt_scene_update"):
             L.rt_scene_update.argtypes = [vp, C.POINTER(MeshDesc), C.POINTER(UpdateStats)]
             L.rt_debug_scene_records.argtypes = [vp, C.c_int32, C.c_int64, vp, C.POINTER(C.c_int64)]
+        # device-resident updates (as above)
+        if hasattr(L, "rt_scene_update_device"):
+            L.rt_scene_update_device.argtypes = [vp, C.POINTER(DeviceGeometry), vp, C.POINTER(UpdateStats)]
         _lib = L
     return _lib
 
@@ -440,6 +448,41 @@ class Scene:
         st = UpdateStats()
         check(lib().rt_scene_update(self.h, C.byref(d), C.byref(st) if stats else None))
         self.mesh = mesh
+        return st.as_dict() if stats else None
+
+    def update_device(self, vertices, vertex_normals, face_normals, model_matrix=None, materials=None, stats=False,
+                      stream=None):
+        """rt_scene_update_device: the scene's geometry replaced from device tensors (torch CUDA tensors or anything
+        with data_ptr(): float32, contiguous, [nv,4] / [nv,3] / [nf,3]); the whole update runs on the device.
+        model_matrix: 16 floats, column-major (None keeps the scene's); materials: a Material array as
+        Mesh.export()["mats"] describes it, float32 [n_materials,12] (None keeps the scene's). stream: the stream
+        the tensors were produced on (default: torch's current stream). Afterwards every query gives the bits of
+        a scene freshly created from the same arrays. stats: return rt_update_stats as a dict."""
+        i = self.info()
+        nv, nf = i["n_vertices"], i["n_faces"]
+        _check_device_array(vertices, "float32", (nv, 4), "update_device: vertices")
+        _check_device_array(vertex_normals, "float32", (nv, 3), "update_device: vertex_normals")
+        _check_device_array(face_normals, "float32", (nf, 3), "update_device: face_normals")
+        g = DeviceGeometry()
+        g.vertices, g.vertex_normals, g.face_normals = (int(x.data_ptr()) or None for x in (vertices, vertex_normals, face_normals))
+        keep = []
+        if model_matrix is not None:
+            m = np.ascontiguousarray(np.asarray(model_matrix, np.float32).reshape(16))
+            keep.append(m)
+            g.shape_model_matrix = m.ctypes.data
+        if materials is not None:
+            mt = np.ascontiguousarray(np.asarray(materials, np.float32).reshape(-1, 12))
+            keep.append(mt)
+            g.materials = mt.ctypes.data
+        if stream is None:
+            try:
+                import torch
+                stream = torch.cuda.current_stream(vertices.device)
+            except (ImportError, AttributeError, TypeError, ValueError):  # (no torch, or no CUDA tensor: the library refuses it)
+                stream = None
+        st = UpdateStats()
+        check(lib().rt_scene_update_device(self.h, C.byref(g), _stream_ptr(stream), C.byref(st) if stats else None))
+        self.mesh = None  # (the mesh the scene was made of no longer describes it; as a loaded scene, it has none)
         return st.as_dict() if stats else None
 
     def records(self, which):
