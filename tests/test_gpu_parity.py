@@ -204,13 +204,13 @@ def test_stats_counting_run(rt, soup):
 def variant_frames_identical(rt, scenes, bits, extra=()):
     """Render bunny (PRIMARY + FULL, 1080p) and the 1M soup (FULL 640x360, PRIMARY 1000x563) with the default
     kernels and with kernel variant `bits`; returns the cases whose rgb / face / t differ. extra: further
-    (scene, W, H, mode) cases."""
+    (scene, W, H, mode) cases, or (scene, W, H, mode, (dx, dy, dz)) with the flycam's translation."""
     bunny, soup = scenes
     cases = [(bunny, 1920, 1080, rt.RT_MODE_PRIMARY), (bunny, 1920, 1080, rt.RT_MODE_FULL),
              (soup, 640, 360, rt.RT_MODE_FULL), (soup, 1000, 563, rt.RT_MODE_PRIMARY)] + list(extra)
     bad = []
-    for sc, W, H, m in cases:
-        cam = rt.flycam(W, H, 0, 0, 20)
+    for sc, W, H, m, *at in cases:
+        cam = rt.flycam(W, H, *(at[0] if at else (0, 0, 20)))
         prev = rt.set_variant(0)
         try:
             ref = sc.render(cam, rt.DEFAULT_LIGHTS, W, H, mode=m, want_hits=True)
